@@ -2,7 +2,7 @@
 """bench.py -- WAN training-steps/sec on the BASELINE.json headline workload:
 d=20 time-independent cube (Ex4_1 functions), N_r = N_b = 4096 paths, N_t = 32, YAML hyper-parameters, float64.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR]
 N > 1: one rank per GPU.  Started under torch.distributed.run (WORLD_SIZE set) this process IS a rank; started plainly,
 `python bench.py --gpus N` launches `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` itself as
 a child process (before anything touches the GPU), relays rank 0's JSON line and exits with the child's code -- the
@@ -25,9 +25,15 @@ over the same ranks, and reports them under `extras.strong` (steps_per_s of a fi
 strong-scaling curve; `value` stays the weak product); `extras.rccl` records how many ranks the exchange saw and whether it
 ran inside the captured sub-step graphs.
 
-Timed region: `--steps` sub-steps cycling g, g, d (rounded UP to whole cycles so that every region holds the same mix),
-repeated `--repeats` times back to back, each repeat bracketed by barrier + synchronize; the reported figure is the MEDIAN
-repeat (`ms_per_step` x `steps` = that repeat's wall time; all repeats are listed in extras.repeat_ms).
+Timed region: exactly `--steps` sub-steps cycling g, g, d (the cycle runs on from the warm-up, which is padded so that the
+first timed sub-step is a generator one), repeated `--repeats` times back to back (default once), each repeat bracketed by
+barrier + synchronize; the reported figure is the MEDIAN repeat (`ms_per_step` x `steps` = that repeat's wall time; all
+repeats are listed in extras.repeat_ms).
+
+`--dump-outputs DIR`: after the timed regions, rank 0 writes what the timed path left its caller after its last sub-step,
+float64, as DIR/<name>.npy: `theta` and `phi` (the updated parameters of u_theta and of the test network), `loss_u`
+and `loss_v` (Engine.loss_u() / loss_v()), `grad_u` and `grad_v` (the gradients the last generator / discriminator Adam
+update applied).  The inputs are seeded, so two builds run with the same arguments can be compared array by array.
 
 Prints ONE JSON line (rank 0).  Extra objects: `roofline` for the dominant kernel (HIP-event timed on the launch
 stream), `cpu_baseline` (the oracle = CPU restatement of the reference, timed on this host, N=1 only).
@@ -87,7 +93,9 @@ def main():
     ap.add_argument('--n_r', type=int, default=4096)
     ap.add_argument('--n_b', type=int, default=4096)
     ap.add_argument('--n_t', type=int, default=32)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps sub-steps each; the median is reported')
+    ap.add_argument('--repeats', type=int, default=1, help='timed regions of --steps sub-steps each; the median is reported')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the timed path '
+                    'computed in its last sub-step as DIR/<name>.npy (float64)')
     ap.add_argument('--global-paths', type=int, default=0, help='strong scaling: a fixed global batch of this many interior '
                     '(and boundary) paths, sharded over the ranks (configs[2]: --dim 50 --n_t 64 --global-paths 16384; '
                     'configs[3]: --dim 100 --global-paths 65536)')
@@ -139,9 +147,8 @@ def main():
         args.n_r = args.n_b = base + (1 if rank < rem else 0)
     params = workload_params(args.dim, args.n_r, args.n_b, args.n_t)
     n_glob = args.global_paths if strong else args.n_r * size
-    steps_requested, warmup_requested = args.steps, args.warmup
-    args.steps = -(-args.steps // 3) * 3                  # whole g, g, d cycles (never fewer than requested)
-    args.warmup = -(-args.warmup // 3) * 3
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     torch.manual_seed(0)                                  # identical initial parameters and time grid on every rank
     S = NODE_WAN_solver(params, P.func_a, P.func_b, P.func_c, P.func_h, P.func_f, P.func_g, dev, './',
@@ -164,25 +171,31 @@ def main():
         torch.cuda.synchronize()
 
     def timed_regions(eng_, G_, steps, warmup, repeats):
-        """`repeats` timed regions of `steps` sub-steps (whole g, g, d cycles) of group G_, each bracketed by barrier +
-        synchronize, every one as long as its slowest rank; returns (seconds per region, untimed extra warm-up sub-steps)"""
-        def run_(n, offset=0):
-            for i in range(n):
-                if schedule[(offset + i) % 3] == 'g':
+        """`repeats` timed regions of exactly `steps` sub-steps of group G_ (the g, g, d cycle running on across them), each
+        bracketed by barrier + synchronize, every one as long as its slowest rank; returns (seconds per region, untimed extra
+        warm-up sub-steps)"""
+        pos = [0]                                         # sub-steps run so far: position in the g, g, d cycle
+
+        def run_(n):
+            for _ in range(n):
+                if schedule[pos[0] % 3] == 'g':
                     eng_.generator_step(G_)
                 else:
                     eng_.discriminator_step(G_)
+                pos[0] += 1
         run_(warmup)
         # The shader clock needs ~30 ms of load to settle (repeats of a 3 ms region: 3.48, 3.44, 3.32, 3.25, 3.20 ms): when the
-        # requested warm-up is shorter than 54 sub-steps, whole untimed cycles are added up to that (extras.extra_warmup_steps)
+        # requested warm-up is shorter than 54 sub-steps, untimed sub-steps are added up to that, and up to a whole cycle so that
+        # the first timed sub-step is a generator one (extras.extra_warmup_steps)
         # (a fixed count, not a timed loop: every rank must run the same number of sub-steps -- they contain collectives)
         extra = max(0, 54 - warmup)
+        extra += -(warmup + extra) % 3
         run_(extra)
         region_ = []
         for _ in range(max(repeats, 1)):
             barrier()
             t0 = time.perf_counter()
-            run_(steps)                                   # (steps and warmup are whole cycles: every region starts at g)
+            run_(steps)
             torch.cuda.synchronize()
             barrier()
             region_.append(time.perf_counter() - t0)
@@ -202,6 +215,14 @@ def main():
 
     region, extra_warmup = timed_regions(eng, G, args.steps, args.warmup, args.repeats)
     elapsed = sorted(region)[len(region) // 2]            # median repeat
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller after its last sub-step (before anything below steps the engine again)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dump = {'theta': eng.theta.data, 'phi': eng.phi.data, 'loss_u': eng.loss_u().reshape(1), 'loss_v': eng.loss_v().reshape(1),
+                'grad_u': eng.grad_u, 'grad_v': eng.grad_v}
+        for name, t in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), t.detach().to('cpu', torch.float64).numpy())
     steps_per_s = args.steps / elapsed
     finite = bool(torch.isfinite(eng.scal[4]).item() and torch.isfinite(eng.theta.data).all().item())
 
@@ -465,8 +486,10 @@ def main():
         Xh = hold.interior(16384)
         torch.set_rng_state(rng)
         cwd = os.getcwd()
-        os.makedirs('/tmp/xnwan_bench', exist_ok=True)
-        os.chdir('/tmp/xnwan_bench')
+        import shutil
+        import tempfile
+        work = tempfile.mkdtemp(prefix='xnwan_bench_')     # train() writes its JSON logs and weights into the working directory
+        os.chdir(work)
         traj, wall, done, calls = [], 0.0, 0, []
         try:
             while done < args.train_iters:
@@ -515,7 +538,7 @@ def main():
             import numpy as np
             import configs.Ex4_3_funcs as P3
             c5 = {}
-            os.chdir('/tmp/xnwan_bench')
+            os.chdir(work)
             for name in ('NSphere_TCone', 'NSphere_THourglass'):
                 p5 = dict(params, dim=10, N_t=20, N_r=8192, N_b=8192, T0=0, T=1, shape_param=1.0, alpha=1e4, domain=name, iterations=3)
                 torch.manual_seed(0)
@@ -535,6 +558,7 @@ def main():
             extras['train_config5_ms_per_outer_iteration'] = {'error': repr(e)[:200]}
         finally:
             os.chdir(cwd)
+            shutil.rmtree(work, ignore_errors=True)
 
     # ---- CPU baseline: the oracle (port of the reference's CPU/PyTorch path), bounded sample ---------------------------
     cpu = None
@@ -586,7 +610,7 @@ def main():
             'metric': ('WAN training-steps/sec (optimiser sub-steps, d=%d cube, %d global paths)' % (s['dim'], n_glob)) if strong
                       else 'WAN training-steps/sec (optimiser sub-steps, d=20 cube, N_r=4096 paths per GPU)',
             'value': round(steps_per_s * (1 if strong else size), 3), 'unit': 'steps/s', 'n_gpus': size, 'steps': args.steps,
-            'warmup': args.warmup, 'steps_requested': steps_requested, 'warmup_requested': warmup_requested,
+            'warmup': args.warmup, 'repeats': max(args.repeats, 1),
             'ms_per_step': round(1e3 * elapsed / args.steps, 4), 'higher_is_better': True,
             'scaling': 'strong' if strong else 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
             'config': {'workload': ('Ex4_1 cube d=%d, %d global paths (interior and boundary) sharded over %d GPU(s), N_t=%d, midpoint, n1=2 n2=1'
