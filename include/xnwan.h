@@ -118,6 +118,44 @@ typedef struct { const double* xT; const double* start; const double* Y; const d
 int xw_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
                      int method, int L, int d, int H, int K, int m, int mode, void* stream);
 
+/* ---- solver 'dopri5': torchdiffeq's adaptive Dormand-Prince 5(4) (the default method of odeint, src/model.py:103-106) -----
+ * One step size per JOB (= one odeint call of the reference: a group of paths), chosen on the device: every attempt is one
+ * launch for all jobs, the last block of a job to finish it reduces the scaled error (RMS over N x Hn entries, Hn = the network's
+ * u_hidden_dim; zero padding adds exact zeros) in block order and advances the job's controller.  Restated from the published
+ * algorithm (torchdiffeq 0.1.x, absent from the reference tree: parity unpinned); defaults rtol 1e-7, atol 1e-9, safety 0.9,
+ * ifactor 10, dfactor 0.2.  Outputs at the sample times t[L] from the quartic dense output of the first accepted step that covers
+ * them; steps are never clipped to the sample times.  Any width / depth the stepper serves (H, K, m of the theta blob).
+ *   ctl[xw_dopri5_ctl_size()]: the job's controller, ZEROED by the caller before xw_dopri5_init; slots
+ *     0 t0  1 dt  2 accepted steps  3 attempts  4 done (!= 0)  5 status (XW_DOPRI_*)  8 last error ratio
+ *     9 min |ratio - 1| over the attempts (how close a decision came to the threshold)  (6, 7: init scratch; 15: ticket)
+ *   work[xw_dopri5_work_size(N)]: per-block partial sums
+ *   record: rec_y[cap + 1][H][N] the states at the accepted grid points, rec_t[cap + 1] the grid, rec_h[cap] the step sizes;
+ *     an attempt writes its candidate into slot n_acc + 1 and never past `cap` (status XW_DOPRI_CAPACITY instead): the caller
+ *     grows the record so that cap >= n_acc + (attempts it enqueues)
+ *   fbuf[2][H][N]: f at the current grid point (FSAL), the buffer of the parity of n_acc
+ *   u[L,N], Y[L,H,N] (Y may be NULL): outputs, as xw_ode_fwd */
+#define XW_DOPRI_CTL 16
+#define XW_DOPRI_UNDERFLOW 1   /* t0 + dt == t0 (torchdiffeq asserts it) */
+#define XW_DOPRI_STEPS 2       /* max_steps accepted steps without reaching t[L-1] */
+#define XW_DOPRI_NONFINITE 3   /* the error ratio is NaN */
+#define XW_DOPRI_CAPACITY 4    /* the record is full (a caller error) */
+typedef struct { const double* xT; const double* start; double* u; double* Y; double* rec_y; double* rec_t; double* rec_h;
+                 double* fbuf; double* ctl; double* work; int N; int cap; } XwDopriJob;
+int xw_dopri5_ctl_size(void);
+int xw_dopri5_work_size(int N);
+/* up to 8 jobs per call; Hn: the network's u_hidden_dim (<= H) -- the divisor of the RMS norms.  Init: y0, f0, the first step
+ * (torchdiffeq _select_initial_step, order 4), output l = 0.  Attempts: enqueue n attempt launches (jobs that are done return at
+ * once); max_steps: the limit on accepted steps (status XW_DOPRI_STEPS). */
+int xw_dopri5_init(const XwDopriJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K, int m,
+                   int Hn, double rtol, double atol, void* stream);
+int xw_dopri5_attempts(const XwDopriJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K,
+                       int m, int Hn, double rtol, double atol, int max_steps, int n, void* stream);
+/* Reverse of the accepted steps of a finished forward pass (the record and the controller it left), step sizes and grid as
+ * constants; b: the sweep job as for xw_ode_bwd_multi (b.Y and b.act are not read), mode bits 0..2 as there. */
+typedef struct { XwOdeBwdJob b; const double* rec_y; const double* rec_t; const double* rec_h; const double* ctl; } XwDopriSweepJob;
+int xw_dopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K,
+                    int m, int mode, void* stream);
+
 /* ---- v_phi: discriminator.forward (src/model.py:37-47) + d/dt by forward-mode ------------------------------------
  * Path mode (tpp == NULL): point (l,n) = (t[l], x_n).  Point mode (tpp != NULL): L must be 1, point n = (tpp[n], x_n).
  * v[L,N] out; vt[L,N] out = dv/dt (may be NULL).

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('XW_LIBRARY') or os.path.join(_HERE, 'libxnwan.so')   # (override: kernel experiments only)
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 c_f32p = ctypes.c_void_p   # coordinates / time grid: const double* (device)   [name kept from the float32 era]
 c_f64p = ctypes.c_void_p   # double*       (device)
@@ -26,6 +26,15 @@ class XwOdeBwdJob(ctypes.Structure):
                 ('gslab', c_vp), ('N', c_int), ('res_first_only', c_int), ('res_u', c_vp), ('res_ref', c_vp),
                 ('res_coef', ctypes.c_double), ('res_base', ctypes.c_double), ('res_w_per_point', c_int), ('res_w', c_vp),
                 ('res_c', c_vp), ('res_cp', c_vp), ('res_kappa2', ctypes.c_double)]
+
+
+class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('u', c_vp), ('Y', c_vp), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp),
+                ('fbuf', c_vp), ('ctl', c_vp), ('work', c_vp), ('N', c_int), ('cap', c_int)]
+
+
+class XwDopriSweepJob(ctypes.Structure):  # ... and of the sweep
+    _fields_ = [('b', XwOdeBwdJob), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp), ('ctl', c_vp)]
 
 
 class XwGroup(ctypes.Structure):           # include/xnwan.h: one group of paths for xw_substep_gen / xw_substep_disc
@@ -62,6 +71,13 @@ SIGNATURES = {
     'xw_ode_bwd_slabs': [c_int],
     'xw_ode_act_rows': [c_int, c_int, c_int, c_int],
     'xw_ode_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
+    'xw_dopri5_ctl_size': [],
+    'xw_dopri5_work_size': [c_int],
+    'xw_dopri5_init': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl,
+                       c_vp],
+    'xw_dopri5_attempts': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl,
+                           c_dbl, c_int, c_int, c_vp],
+    'xw_dopri5_sweep': [ctypes.POINTER(XwDopriSweepJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
     'xw_ode_bwd': [c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                    c_f64p, c_f64p, c_f64p, c_vp],
     'xw_disc_fwd': [c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_int,

@@ -166,6 +166,14 @@ class Engine:
         opt = self.options = options if options is not None else EngineOptions.from_env()
         self.d = setup['dim']
         self.method = KN.method_id(config['solver'])
+        # solver 'dopri5' (DESIGN 8): every forward reads its step controllers back to the host between chunks of attempts, so
+        # no segment that holds one can be captured -- decided here, up front: eager launches on one stream, no fused runner
+        # (xw_substep_* is fixed-grid), no activation store (the sweeps recompute from the step record)
+        self.dopri5 = self.method == KN.DOPRI5
+        self._dopri_recs = {}
+        if self.dopri5 and world is not None:
+            raise XnwanError("solver 'dopri5' runs on one GPU: its step sizes are per group and chosen on the device, and a "
+                             "group sharded over %d ranks would need an exchange per attempted step (not built)" % world.size)
         # config['adjoint'] (src/model.py:103): the sweeps integrate torchdiffeq's continuous adjoint instead of reversing
         # the steps taken (include/xnwan.h, xw_ode_bwd mode bit 3); nabla_x u then only flows through the start value
         self.adjoint = bool(config.get('adjoint', False))
@@ -285,6 +293,8 @@ class Engine:
         self.prio_drop = {'A': int(opt.prio_drop_A) if opt.prio_drop_A is not None else (3 if self.d <= 32 else 2),
                           'X': int(opt.prio_drop_X), 'F': int(opt.prio_drop_F), 'G': int(opt.prio_drop_G)}
         self.use_runner = opt.use_runner      # one C call per eager group sub-step (xw_substep_*)
+        if self.dopri5:
+            self.use_graphs = self.use_streams = self.use_runner = self.keep_activations = False
         # Measured (profiles/r04_shard_sweep.md): forward and the sweep without weight gradients gain on shards up to ~2048
         # paths (0.302 -> 0.272 ms per sub-step at 512 paths, 0.332 -> 0.294 at 1024, 0.375 -> 0.367 at 2048); the narrow sweep
         # WITH weight gradients only ties the two-wave duo sweep (88 against 83 us alone) and is left to XW_NARROW_SET=fxp; at
@@ -1190,11 +1200,11 @@ class Engine:
             self._launch_test_net_here(G)                        # enqueued first: its blocks must be resident before the
         with self._side(1, e0):                                  # stepper's waves spread over the CUs
             fwd = [self._job(G, 'i')] + ([self._job(G, 'b')] if joint else [])
-            KN.ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, narrow=self._narrow_ok(fwd, alone=False, forward=True),
+            self._ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, narrow=self._narrow_ok(fwd, alone=False, forward=True),
                              prio_drop=self.prio_drop['G'])
             if G.Nb and not joint:
                 fwd_b = [self._job(G, 'b')]
-                KN.ode_fwd_multi(fwd_b, G.tb, th, *M, narrow=self._narrow_ok(fwd_b, alone=False, forward=True))
+                self._ode_fwd_multi(fwd_b, G.tb, th, *M, narrow=self._narrow_ok(fwd_b, alone=False, forward=True))
             self._reaction(G)
             e_f = self._mark()
             # Cotangent A (pollution + the initial-value penalty at t_0) and the boundary cotangent are residuals of what
@@ -1212,17 +1222,17 @@ class Engine:
             if not fused_x:
                 with self._side(2, e_f):
                     sweep_x = [self._job(G, 'i', want_x=True)]
-                    KN.ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False, adjoint=self.adjoint,
+                    self._ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False, adjoint=self.adjoint,
                                      narrow=self._narrow_ok(sweep_x, alone=False, params=False))
                     e_x = self._mark()
             sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=fused_x), res=res_A)]
             if joint:
                 sweeps.append(dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b))
-            KN.ode_bwd_multi(sweeps, G.t, th, *M, want_x=fused_x, want_params=True, x_cot_ones=fused_x, adjoint=self.adjoint,
+            self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=fused_x, want_params=True, x_cot_ones=fused_x, adjoint=self.adjoint,
                              narrow=self._narrow_ok(sweeps, alone=False), prio_drop=self.prio_drop['A'])
             if G.Nb and not joint:
                 sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
-                KN.ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
+                self._ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                                  narrow=self._narrow_ok(sweep_b, alone=False))
             e_A = self._mark()
             # The slabs of sweeps A + boundary are summed HERE, beside the tail of sweep B, so that the update at the end of the sub-step
@@ -1242,7 +1252,7 @@ class Engine:
         res_B = dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob,
                      weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck))
         sweep_B = [dict(self._job(G, 'i', None, G.slabB), res=res_B)]
-        KN.ode_bwd_multi(sweep_B, G.t, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
+        self._ode_bwd_multi(sweep_B, G.t, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweep_B, alone=True))
         # the reduction needs nabla_x u (sweep A) and v, not sweep B: it runs behind sweep A on the side stream, next to
         # the tail of sweep B, instead of after it
@@ -1276,7 +1286,7 @@ class Engine:
         with self._side(1, e0):
             fwd = [self._job(G, 'i'), self._job(G, 'b')]
             lone = bool(getattr(G, 'skip_v', False))
-            KN.ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, narrow=self._narrow_ok(fwd, alone=lone, forward=True),
+            self._ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, narrow=self._narrow_ok(fwd, alone=lone, forward=True),
                              prio_drop=self.prio_drop['G'])
             self._reaction(G)
             e_f = self._mark()
@@ -1288,7 +1298,7 @@ class Engine:
         sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=True), res=res_A),
                   dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b),
                   dict(self._job(G, 'i', None, G.slabB), res=res_B)]
-        KN.ode_bwd_multi(sweeps, G.t, th, *M, want_x=True, want_params=True, x_cot_ones=True, adjoint=self.adjoint,
+        self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=True, want_params=True, x_cot_ones=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweeps, alone=bool(getattr(G, 'skip_v', False))))
         G.sumA_ready = False
         self._contract(G, self.adam_u, with_bdry=True)
@@ -1402,10 +1412,10 @@ class Engine:
         if not G.Nb:
             return
         fwd_b = [self._job(G, 'b')]
-        KN.ode_fwd_multi(fwd_b, G.tb, th, *M, narrow=self._narrow_ok(fwd_b, alone=False, forward=True))
+        self._ode_fwd_multi(fwd_b, G.tb, th, *M, narrow=self._narrow_ok(fwd_b, alone=False, forward=True))
         res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
         sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
-        KN.ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
+        self._ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweep_b, alone=False))
         KN.bdry_partials(G.ub, G.g, self.alpha, G.Nbglob, self.scal, G.work_b)
         KN.slab_sum(G.slabA[G.ns_u:], out=self.pack_u[:P])
@@ -1427,11 +1437,11 @@ class Engine:
             # (the only sweep of this sub-step has no weight gradients: the forward stores a seventh of the record)
             fwd = [self._job(G, 'i')]
             lone = bool(getattr(G, 'skip_v', False))          # (the test network is reused: this chain has the chip to itself)
-            KN.ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, act_x_only=True, narrow=self._narrow_ok(fwd, alone=lone, forward=True),
+            self._ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, act_x_only=True, narrow=self._narrow_ok(fwd, alone=lone, forward=True),
                              prio_drop=self.prio_drop['F'])
             self._reaction(G)
             sweep_x = [self._job(G, 'i', want_x=True)]
-            KN.ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False, adjoint=self.adjoint,
+            self._ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False, adjoint=self.adjoint,
                              narrow=self._narrow_ok(sweep_x, alone=lone, params=False), prio_drop=self.prio_drop['X'])
             e_x = self._mark()
         self._join(e_x)
@@ -1588,18 +1598,43 @@ class Engine:
     def loss_v(self):
         return self.scal[5]
 
+    # ---- the stepper launches, for every served solver ------------------------------------------------------------
+    def _ode_fwd_multi(self, jobs, t, th, method, H, K, m, zero16=None, **kw):
+        """KN.ode_fwd_multi; with dopri5 one kernels.dopri5_fwd per 8 jobs, each job's step record kept for its sweep
+        (keyed by the job's sample and grid, which the sweep jobs share)"""
+        if method != KN.DOPRI5:
+            return KN.ode_fwd_multi(jobs, t, th, method, H, K, m, zero16=zero16, **kw)
+        if zero16 is not None:
+            zero16.zero_()
+        o = self.options
+        for i in range(0, len(jobs), KN.DOPRI5_MAXJOBS):
+            part = jobs[i:i + KN.DOPRI5_MAXJOBS]
+            recs = KN.dopri5_fwd([dict(xT=j['xT'], start=j['start'], u=j['u'], Y=j.get('Y')) for j in part], t, th, H, K, m,
+                                 self.config['u_hidden_dim'], chunk=o.dopri5_chunk, max_steps=o.dopri5_max_steps)
+            for j, r in zip(part, recs):
+                self._dopri_recs[(j['xT'].data_ptr(), t.data_ptr())] = r
+
+    def _ode_bwd_multi(self, jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, **kw):
+        """KN.ode_bwd_multi; with dopri5 kernels.dopri5_sweep over the records of the forward that produced these jobs' u"""
+        if method != KN.DOPRI5:
+            return KN.ode_bwd_multi(jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint, **kw)
+        for i in range(0, len(jobs), KN.DOPRI5_MAXJOBS):
+            part = [dict(j, rec=self._dopri_recs[(j['xT'].data_ptr(), t.data_ptr())]) for j in jobs[i:i + KN.DOPRI5_MAXJOBS]]
+            KN.dopri5_sweep(part, t, th, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones)
+
+    def _u_forward(self, xT, t, start):
+        return KN.u_forward(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, self.config['u_hidden_dim'],
+                            chunk=self.options.dopri5_chunk, max_steps=self.options.dopri5_max_steps)
+
     def predict_group(self, G):
         """u_theta on the interior paths of a loaded group as the module returns it, [N, L, 1] -- no path tensor, no callables:
         the group already holds the transposed points, the grid and the start values"""
-        u, _ = KN.ode_fwd(G.xT, G.t, G.start, self.theta.data, self.method, self.H, self.K, self.m, want_Y=False)
-        return u.t().unsqueeze(2)
+        return self._u_forward(G.xT, G.t, G.start).t().unsqueeze(2)
 
     def predict(self, X):
         """u_theta on a group [N, L, d+1] -> [L, N] (diagnostics; no checkpoints kept)"""
         Xd = X.detach()
         starts_T0 = float(Xd[0, 0, 0]) == self.setup['T0']
         s = self.funcs['h'](Xd[:, 0, :]) if starts_T0 else self.funcs['g'](Xd[:, 0, :].unsqueeze(1)).reshape(-1)
-        u, _ = KN.ode_fwd(Xd[:, 0, 1:].to(self.dev).to(F64).t().contiguous(), Xd[0, :, 0].to(self.dev).to(F64).contiguous(),
-                          s.detach().to(self.dev).to(F64).reshape(-1).contiguous(), self.theta.data, self.method,
-                          self.H, self.K, self.m, want_Y=False)
-        return u
+        return self._u_forward(Xd[:, 0, 1:].to(self.dev).to(F64).t().contiguous(), Xd[0, :, 0].to(self.dev).to(F64).contiguous(),
+                               s.detach().to(self.dev).to(F64).reshape(-1).contiguous())

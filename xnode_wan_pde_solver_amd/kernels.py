@@ -5,9 +5,12 @@ Conventions (include/xnwan.h): point arrays are time-major [L, N]; coordinates a
 """
 import torch
 
-from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob
+from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
+DOPRI5 = 3                                 # solver 'dopri5' (adaptive, dopri5_fwd / dopri5_sweep below): not a fixed-grid method id
+ADAPTIVE_REFUSED = ('dopri8', 'bosh3', 'fehlberg2', 'adaptive_heun', 'adams', 'explicit_adams', 'implicit_adams',
+                    'fixed_adams', 'scipy_solver')   # torchdiffeq's other methods: not served
 F32, F64 = torch.float32, torch.float64
 
 
@@ -54,8 +57,11 @@ def _stream():
 
 
 def method_id(name):
+    if name == 'dopri5':
+        return DOPRI5
     if name not in METHODS:
-        raise XnwanError("solver %r is not a fixed-grid scheme of this engine (have: %s)" % (name, sorted(METHODS)))
+        raise XnwanError("solver %r is not served: the fixed-grid schemes %s and the adaptive 'dopri5' are (no other adaptive "
+                         "torchdiffeq method)" % (name, sorted(METHODS)))
     return METHODS[name]
 
 
@@ -169,6 +175,29 @@ def ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, act_x_only=False
     check(lib.xw_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _stream()), 'xw_ode_fwd_multi')
 
 
+def _set_res(a, j, L, N):
+    res = j.get('res')
+    if res is not None:
+        # cotangent formed from a residual inside the sweep (XwOdeBwdJob.res_*): base + coef (u - ref)
+        if j.get('ubar') is not None:
+            raise XnwanError('a sweep job takes a stored cotangent (ubar) or a residual (res), not both')
+        if res.get('weak') is not None:
+            # the weak form's dI/du: coef d(c(u) u)/du v w (+ base v at the last time index); ref = v
+            wk = res['weak']
+            wpp = wk['w'].dim() == 2
+            _chk(res['u'], F64, (L, N), 'res.u'); _chk(res['ref'], F64, (L, N), 'res.ref (v)')
+            _chk(wk['w'], F64, (L, N) if wpp else (N,), 'res.weak.w'); _chk(wk.get('c'), F64, (L, N), 'res.weak.c')
+            _chk(wk.get('cp'), F64, (L, N), 'res.weak.cp')
+            a.res_first_only, a.res_u, a.res_ref = 2, _p(res['u']), _p(res['ref'])
+            a.res_w_per_point, a.res_w, a.res_c, a.res_cp = int(wpp), _p(wk['w']), _p(wk.get('c')), _p(wk.get('cp'))
+            a.res_kappa2 = 2.0 * float(wk.get('ckappa', 0.0))
+        else:
+            first = bool(res['first_only'])
+            _chk(res['u'], F64, (L, N), 'res.u'); _chk(res['ref'], F64, (N,) if first else (L, N), 'res.ref')
+            a.res_first_only, a.res_u, a.res_ref = int(first), _p(res['u']), _p(res['ref'])
+        a.res_coef, a.res_base = float(res['coef']), float(res['base'])
+
+
 def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False, prio_drop=0):
     """jobs: list of dicts(xT, start, Y, ubar or None, gx, gs, gslab); ONE launch for all groups.
     res = dict(u[L,N], ref ([N] with first_only, else [L,N]), coef, base, first_only) instead of ubar: the cotangent
@@ -198,26 +227,7 @@ def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_on
         a.xT, a.start, a.Y, a.ubar, a.N = _p(j['xT']), _p(j['start']), _p(j['Y']), _p(j.get('ubar')), N
         a.act = _p(j.get('act'))
         a.gx, a.gs, a.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
-        res = j.get('res')
-        if res is not None:
-            # cotangent formed from a residual inside the sweep (XwOdeBwdJob.res_*): base + coef (u - ref)
-            if j.get('ubar') is not None:
-                raise XnwanError('a sweep job takes a stored cotangent (ubar) or a residual (res), not both')
-            if res.get('weak') is not None:
-                # the weak form's dI/du: coef d(c(u) u)/du v w (+ base v at the last time index); ref = v
-                wk = res['weak']
-                wpp = wk['w'].dim() == 2
-                _chk(res['u'], F64, (L, N), 'res.u'); _chk(res['ref'], F64, (L, N), 'res.ref (v)')
-                _chk(wk['w'], F64, (L, N) if wpp else (N,), 'res.weak.w'); _chk(wk.get('c'), F64, (L, N), 'res.weak.c')
-                _chk(wk.get('cp'), F64, (L, N), 'res.weak.cp')
-                a.res_first_only, a.res_u, a.res_ref = 2, _p(res['u']), _p(res['ref'])
-                a.res_w_per_point, a.res_w, a.res_c, a.res_cp = int(wpp), _p(wk['w']), _p(wk.get('c')), _p(wk.get('cp'))
-                a.res_kappa2 = 2.0 * float(wk.get('ckappa', 0.0))
-            else:
-                first = bool(res['first_only'])
-                _chk(res['u'], F64, (L, N), 'res.u'); _chk(res['ref'], F64, (N,) if first else (L, N), 'res.ref')
-                a.res_first_only, a.res_u, a.res_ref = int(first), _p(res['u']), _p(res['ref'])
-            a.res_coef, a.res_base = float(res['coef']), float(res['base'])
+        _set_res(a, j, L, N)
     if x_cot_ones and not (want_x and want_params):
         raise XnwanError('x_cot_ones needs want_x and want_params')
     if x_cot_ones and adjoint:
@@ -266,6 +276,170 @@ def ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_par
                          _p(gx if want_x else None), _p(gs if want_x else None), _p(gslab if want_params else None),
                          _stream()), 'xw_ode_bwd')
     return (gx if want_x else None), (gs if want_x else None), (gslab if want_params else None)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# solver 'dopri5' (csrc/xw_dopri.hip, include/xnwan.h): torchdiffeq's adaptive Dormand-Prince 5(4), one step size per job
+# ----------------------------------------------------------------------------------------------------------------------
+DOPRI5_RTOL, DOPRI5_ATOL = 1e-7, 1e-9      # torchdiffeq's defaults (the reference passes neither)
+DOPRI5_CHUNK, DOPRI5_MAX_STEPS = 8, 10000  # attempts per host check; accepted steps per call (defaults of EngineOptions.dopri5_*)
+DOPRI5_MAXJOBS = 8                         # jobs per launch (csrc/xw_dopri.hip XW_DOPRI_MAXJOBS)
+CTL_T0, CTL_DT, CTL_NACC, CTL_NATT, CTL_DONE, CTL_STATUS, CTL_RATIO, CTL_GAP = 0, 1, 2, 3, 4, 5, 8, 9
+
+
+def dopri5_status_message(status, ctl, max_steps):
+    """the XnwanError text for a controller that ended with `status` (include/xnwan.h XW_DOPRI_*); None for status 0.
+    ctl: the job's controller as a host sequence (t0, dt, ... slots)"""
+    status = int(status)
+    if status == 0:
+        return None
+    where = 'at t = %.17g after %d accepted steps / %d attempts' % (float(ctl[CTL_T0]), int(ctl[CTL_NACC]), int(ctl[CTL_NATT]))
+    if status == 1:
+        return "solver 'dopri5': underflow in dt %.17g %s (t0 + dt == t0)" % (float(ctl[CTL_DT]), where)
+    if status == 2:
+        return ("solver 'dopri5': the step limit of %d accepted steps (EngineOptions.dopri5_max_steps / XNODE.dopri5_max_steps) "
+                "was reached before the last sample time, %s" % (int(max_steps), where))
+    if status == 3:
+        return "solver 'dopri5': the error ratio is not finite (NaN in the field?) %s" % where
+    if status == 4:
+        return "solver 'dopri5': the step record is full %s -- the host did not grow it ahead of the attempts" % where
+    return "solver 'dopri5': unknown controller status %d %s" % (status, where)
+
+
+class Dopri5Record:
+    """What a dopri5 forward pass leaves for its sweep: per job the states at the accepted grid points, the grid, the step
+    sizes and the controller.  `n_acc`, `n_att`, `min_gap`, `grid` (host float64 tensor) and `steps` (accepted (t0, dt)) are
+    filled when dopri5_fwd returns."""
+
+    def __init__(self, N, H, cap, dev):
+        self.N, self.H, self.cap = N, H, cap
+        self.rec_y = torch.empty(cap + 1, H, N, dtype=F64, device=dev)
+        self.rec_t = torch.empty(cap + 1, dtype=F64, device=dev)
+        self.rec_h = torch.empty(max(cap, 1), dtype=F64, device=dev)
+        self.fbuf = torch.empty(2, H, N, dtype=F64, device=dev)
+        self.work = torch.empty(lib.xw_dopri5_work_size(N), dtype=F64, device=dev)
+        self.n_acc = self.n_att = 0
+        self.grid = self.min_gap = self.steps = None
+
+    def grow(self, cap, n_acc):
+        """a larger record holding the first n_acc + 1 grid points of this one (stream-ordered copies)"""
+        y, tt, h = self.rec_y, self.rec_t, self.rec_h
+        self.rec_y = torch.empty(cap + 1, self.H, self.N, dtype=F64, device=y.device)
+        self.rec_t = torch.empty(cap + 1, dtype=F64, device=y.device)
+        self.rec_h = torch.empty(cap, dtype=F64, device=y.device)
+        self.rec_y[:n_acc + 1].copy_(y[:n_acc + 1])
+        self.rec_t[:n_acc + 1].copy_(tt[:n_acc + 1])
+        self.rec_h[:n_acc].copy_(h[:n_acc])
+        self.cap = cap
+
+
+def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS,
+               cap=None):
+    """u_theta with solver 'dopri5' for jobs = list of dicts(xT[d,N], start[N], u[L,N], Y[L,H,N] or None) sharing t and theta;
+    one step size per job (one odeint call of the reference).  Hn: the network's u_hidden_dim (the RMS norms divide by N Hn).
+    Enqueues the init launches, then attempts in chunks of `chunk` launches; after each chunk the controllers are copied to
+    page-locked host memory and ONE event is waited on; the records grow on the host before the next chunk, so that no attempt
+    can write past them.  Returns a Dopri5Record per job (for dopri5_sweep and diagnostics).  A controller that ends with a bad
+    status raises XnwanError.  Synchronises with the host: a dopri5 forward cannot be captured into a graph."""
+    _need_gpu()
+    if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
+        raise XnwanError('dopri5_fwd: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
+    chunk, max_steps = int(chunk), int(max_steps)
+    if chunk < 1 or max_steps < 1:
+        raise XnwanError('dopri5_fwd: chunk and max_steps must be >= 1')
+    L = t.shape[0]
+    d = jobs[0]['xT'].shape[0]
+    dev = t.device
+    _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    nj = len(jobs)
+    ctl = torch.zeros(nj, lib.xw_dopri5_ctl_size(), dtype=F64, device=dev)
+    mirror = torch.empty(ctl.shape, dtype=F64, pin_memory=True)
+    recs = []
+    for j in jobs:
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
+        _chk(j.get('Y'), F64, (L, H, N), 'Y')
+        recs.append(Dopri5Record(N, H, int(cap) if cap else 4 * chunk, dev))
+    arr = (XwDopriJob * nj)()
+
+    def fill():
+        for i, (a, j, r) in enumerate(zip(arr, jobs, recs)):
+            a.xT, a.start, a.u, a.Y = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y'))
+            a.rec_y, a.rec_t, a.rec_h, a.fbuf = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.fbuf)
+            a.ctl, a.work, a.N, a.cap = _p(ctl[i]), _p(r.work), r.N, r.cap
+    args = (_p(t), _p(theta), L, d, H, K, m, int(Hn), float(rtol), float(atol))
+    fill()
+    check(lib.xw_dopri5_init(arr, nj, *args, _stream()), 'xw_dopri5_init')
+    ev = torch.cuda.Event()
+    n_acc = [0] * nj
+    while True:
+        grown = False
+        for i, r in enumerate(recs):
+            if r.cap < n_acc[i] + chunk:
+                r.grow(max(2 * r.cap, n_acc[i] + chunk), n_acc[i])
+                grown = True
+        if grown:
+            fill()
+        check(lib.xw_dopri5_attempts(arr, nj, *args, max_steps, chunk, _stream()), 'xw_dopri5_attempts')
+        mirror.copy_(ctl, non_blocking=True)
+        ev.record()
+        ev.synchronize()
+        n_acc = [int(c) for c in mirror[:, CTL_NACC].tolist()]
+        if all(mirror[:, CTL_DONE] != 0):
+            break
+    host = mirror.clone()
+    for i, r in enumerate(recs):
+        msg = dopri5_status_message(host[i, CTL_STATUS], host[i], max_steps)
+        if msg is not None:
+            raise XnwanError(msg)
+        r.ctl = ctl[i]
+        r.n_acc, r.n_att, r.min_gap = int(host[i, CTL_NACC]), int(host[i, CTL_NATT]), float(host[i, CTL_GAP])
+        r.grid = r.rec_t[:r.n_acc + 1].cpu()
+        r.steps = list(zip(r.grid[:-1].tolist(), r.rec_h[:r.n_acc].cpu().tolist()))     # accepted (t0, dt)
+    return recs
+
+
+def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS):
+    """u[L,N] of one group with any served solver: ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
+    Hn: the network's u_hidden_dim (dopri5's RMS norms)"""
+    if method != DOPRI5:
+        return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
+    u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)
+    dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps)
+    return u
+
+
+def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False):
+    """reverse of the accepted steps of dopri5_fwd (step sizes and grid as constants: DESIGN 8).  jobs: list of dicts as for
+    ode_bwd_multi (xT, start, ubar or res, gx, gs, gslab; no Y / act) plus 'rec': the job's Dopri5Record.  Same outputs and
+    layouts as ode_bwd_multi (mode bits 0..2)."""
+    _need_gpu()
+    if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
+        raise XnwanError('dopri5_sweep: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
+    if x_cot_ones and not (want_x and want_params):
+        raise XnwanError('x_cot_ones needs want_x and want_params')
+    L = t.shape[0]
+    d = jobs[0]['xT'].shape[0]
+    P = theta_size(d, H, K)
+    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    arr = (XwDopriSweepJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        r = j['rec']
+        if r.N != N or r.H != H:
+            raise XnwanError('dopri5_sweep: the record is for N = %d, H = %d' % (r.N, r.H))
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j.get('ubar'), F64, (L, N), 'ubar')
+        if want_x and not (x_cot_ones and j.get('gx') is None):
+            _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
+        if want_params:
+            _chk(j['gslab'], F64, (ode_bwd_slabs(N), P), 'gslab')
+        b = a.b
+        b.xT, b.start, b.Y, b.act, b.ubar, b.N = _p(j['xT']), _p(j['start']), 0, 0, _p(j.get('ubar')), N
+        b.gx, b.gs, b.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
+        _set_res(b, j, L, N)
+        a.rec_y, a.rec_t, a.rec_h, a.ctl = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.ctl)
+    mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0)
+    check(lib.xw_dopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _stream()), 'xw_dopri5_sweep')
 
 
 DISC_UNROLLED_DEPTH = 9   # v_layers of the reference's YAML: the depth the recomputing reverse kernels are compiled for

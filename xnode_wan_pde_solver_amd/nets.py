@@ -156,6 +156,49 @@ class _OdeFn(torch.autograd.Function):
         return (gX, gS, None) + tuple(gp)
 
 
+class _Dopri5Fn(torch.autograd.Function):
+    """u_net(X).backward() with solver 'dopri5' (kernels.dopri5_fwd / dopri5_sweep).  A plain autograd Function, not a
+    torch.library operator like _OdeFn: what the backward pass reverses is the step record of the forward pass, whose size
+    (the accepted steps) is known only once the forward pass has run -- no fake kernel can state it -- so the record rides on
+    ctx.  Step sizes are constants of the backward pass."""
+
+    @staticmethod
+    def forward(ctx, X, start, net, *params):
+        blob = net.blob
+        blob.check_alias()
+        xT = X[:, 0, 1:].detach().to(F64).t().contiguous()
+        t = X[0, :, 0].detach().to(F64).contiguous()
+        s = start.detach().to(F64).reshape(-1).contiguous()
+        N, L = X.shape[0], X.shape[1]
+        u = torch.empty(L, N, dtype=F64, device=X.device)
+        rec, = KN.dopri5_fwd([dict(xT=xT, start=s, u=u)], t, blob.data, net.kdims[0], net.kdims[1], net.num_layers,
+                             net.hidden_dim, rtol=net.rtol, atol=net.atol, chunk=net.dopri5_chunk, max_steps=net.dopri5_max_steps)
+        net.last_dopri5 = rec
+        ctx.net, ctx.rec, ctx.x_dtype, ctx.s_shape, ctx.s_dtype = net, rec, X.dtype, start.shape, start.dtype
+        ctx.save_for_backward(xT, t, s)
+        return u.t().unsqueeze(2).contiguous()
+
+    @staticmethod
+    def backward(ctx, gu):
+        net = ctx.net
+        xT, t, s = ctx.saved_tensors
+        (d, N), (H, K) = xT.shape, net.kdims
+        want_p = any(ctx.needs_input_grad[3:])
+        gx = torch.empty(d, N, dtype=F64, device=gu.device)
+        gs = torch.empty(N, dtype=F64, device=gu.device)
+        gslab = torch.empty(KN.ode_bwd_slabs(N), KN.theta_size(d, H, K), dtype=F64, device=gu.device) if want_p else None
+        ubar = gu.squeeze(2).t().contiguous().to(F64)
+        KN.dopri5_sweep([dict(xT=xT, start=s, ubar=ubar, gx=gx, gs=gs, gslab=gslab, rec=ctx.rec)], t, net.blob.data, H, K,
+                        net.num_layers, want_x=True, want_params=want_p)
+        gX = None
+        if ctx.needs_input_grad[0]:
+            gX = torch.zeros((N, t.shape[0], d + 1), dtype=ctx.x_dtype, device=gu.device)
+            gX[:, 0, 1:] = gx.t().to(ctx.x_dtype)
+        gS = gs.view(ctx.s_shape).to(ctx.s_dtype) if ctx.needs_input_grad[1] else None
+        gp = net.blob.split(KN.slab_sum(gslab)) if want_p else [None] * len(net.blob.params)
+        return (gX, gS, None) + tuple(gp)
+
+
 class _DiscFn(torch.autograd.Function):
     """v_net(XV).backward() through xnwan::testnet_forward / testnet_backward (ops.py)"""
 
@@ -209,6 +252,12 @@ class XNODE(nn.Module):
         self.h, self.g, self.setup, self.num_layers, self.domain = func_h, func_g, setup, num_layers, domain
         self.solver, self.min_steps, self.adjoint = solver, min_steps, adjoint
         self.method = KN.method_id(solver)
+        if self.method == KN.DOPRI5 and adjoint:
+            raise XnwanError("solver 'dopri5' with adjoint=True is not served: the sweep reverses the accepted steps (the "
+                             "discrete adjoint, step sizes as constants); torchdiffeq's continuous adjoint of an adaptive solve is not built")
+        self.rtol, self.atol = KN.DOPRI5_RTOL, KN.DOPRI5_ATOL        # (dopri5: torchdiffeq's defaults, as the reference gets them)
+        self.dopri5_chunk, self.dopri5_max_steps = KN.DOPRI5_CHUNK, KN.DOPRI5_MAX_STEPS
+        self._ode_fn = _Dopri5Fn if self.method == KN.DOPRI5 else _OdeFn
         self.initial_layers = nn.Sequential(nn.Linear(1, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, hidden_dim),
                                             nn.ReLU(), nn.Linear(hidden_dim, hidden_dim)).double()
         self.ODE_rhs = HiddenField(hidden_dim, setup, num_layers, hidden_hidden_dim)
@@ -257,6 +306,9 @@ class XNODE(nn.Module):
         if not starts_at_T0 and not known:
             on_boundary = float(torch.max(self.domain.func_w(inputs[:, 0, :].detach().unsqueeze(1)))) < 1e-5
             if not on_boundary:
+                if self.method == KN.DOPRI5:
+                    raise XnwanError("solver 'dopri5': paths that start neither at T0 nor on the boundary (the evaluation path over "
+                                     "domain.bound_pad's densified grids) are not served")
                 # evaluation of points that are neither at T0 nor on the boundary (src/model.py:92-106): integrate from T0
                 # over the densified grid of domain.bound_pad / fillt and keep the states at the requested times
                 path_i, gather, filled = self.domain.bound_pad(inputs.detach())
@@ -269,16 +321,16 @@ class XNODE(nn.Module):
                         grid = grid.to(inputs.device).to(inputs.dtype).reshape(-1)
                         padded = inputs[:, :1, :].repeat(1, grid.shape[0], 1)
                         padded[:, :, 0] = grid.view(1, -1)
-                        out = _OdeFn.apply(padded.to(dev), start.to(dev), self, *self.blob.params)
+                        out = self._ode_fn.apply(padded.to(dev), start.to(dev), self, *self.blob.params)
                         outs.append(out[rows.to(dev)][:, cols.long().to(dev), :])
                     return torch.cat(outs, dim=0)
                 grid = filled.to(inputs.device).to(inputs.dtype)
                 padded = inputs[:, :1, :].repeat(1, grid.shape[0], 1)
                 padded[:, :, 0] = grid.view(1, -1)
                 start = self.start_values(inputs)
-                out = _OdeFn.apply(padded.to(dev), start.to(dev), self, *self.blob.params)
+                out = self._ode_fn.apply(padded.to(dev), start.to(dev), self, *self.blob.params)
                 return out[:, gather.long().to(dev), :]
-        out = _OdeFn.apply(inputs.to(dev), self.start_values(inputs, starts_at_T0).to(dev), self, *self.blob.params)
+        out = self._ode_fn.apply(inputs.to(dev), self.start_values(inputs, starts_at_T0).to(dev), self, *self.blob.params)
         if inputs.shape[1] == 1 and starts_at_T0:
             return out[:, 0, :]                                   # reference returns [N, 1] here (src/model.py:89-91)
         return out

@@ -59,6 +59,9 @@ class EngineOptions:
     defer_list_readback: bool = True    # XW_DEFER_LIST: list domains -- one read-back per outer iteration
     sampler_process: bool = True        # XW_SAMPLER_PROCESS: ball domains -- samples drawn by a forked child process
     show_plan: bool = False             # XW_SHOW_PLAN: train() prints solver.plan() once per call
+    # ---- solver 'dopri5' (kernels.dopri5_fwd) ------------------------------------------------------------------------------------
+    dopri5_chunk: int = 8               # XW_DOPRI5_CHUNK: attempt launches enqueued between two read-backs of the step controllers
+    dopri5_max_steps: int = 10000       # XW_DOPRI5_MAX_STEPS: accepted steps per forward before XnwanError
     # ---- several GPUs (dist.World) ------------------------------------------------------------------------------------------
     replicate_below: int = 16           # XW_REPLICATE_BELOW: groups with fewer paths per rank are computed whole on every rank
     native_allreduce: bool = True       # XW_NATIVE_ALLREDUCE: the exchange through xw_allreduce (RCCL) instead of torch.distributed
@@ -101,6 +104,8 @@ class EngineOptions:
         o.defer_list_readback = _flag('XW_DEFER_LIST', o.defer_list_readback)
         o.sampler_process = _flag('XW_SAMPLER_PROCESS', o.sampler_process)
         o.show_plan = _flag('XW_SHOW_PLAN', o.show_plan)
+        o.dopri5_chunk = _int('XW_DOPRI5_CHUNK', o.dopri5_chunk)
+        o.dopri5_max_steps = _int('XW_DOPRI5_MAX_STEPS', o.dopri5_max_steps)
         o.replicate_below = _int('XW_REPLICATE_BELOW', o.replicate_below)
         o.native_allreduce = _flag('XW_NATIVE_ALLREDUCE', o.native_allreduce)
         return o

@@ -228,6 +228,9 @@ class NODE_WAN_solver:
         self._group_cache = []
         self.config, self.setup, self.iterations = split_params(params)
         self.domain = sampling.resolve_domain(params['domain'])
+        if self.config['solver'] == 'dopri5' and isinstance(self.domain, type) and issubclass(self.domain, sampling._NSphereBase):
+            raise XnwanError("solver 'dopri5' trains on the cube domain only: the ball domains' groups start inside the time interval "
+                             "on per-bucket grids (bound_pad), which the dopri5 path does not serve")
         self.n1, self.n2 = self.config['n1'], self.config['n2']
 
         s = self.setup
@@ -436,8 +439,9 @@ class NODE_WAN_solver:
 
             def u_fn(x):
                 s_k, a_k = next(starts)
-                u, _ = KN.ode_fwd(x[:, 0, 1:].t().contiguous(), x[0, :, 0].contiguous(), s_k.contiguous(), net.blob.data, net.method,
-                                  net.kdims[0], net.kdims[1], net.num_layers, want_Y=False)
+                u = KN.u_forward(x[:, 0, 1:].t().contiguous(), x[0, :, 0].contiguous(), s_k.contiguous(), net.blob.data, net.method,
+                                 net.kdims[0], net.kdims[1], net.num_layers, net.hidden_dim, chunk=self.options.dopri5_chunk,
+                                 max_steps=self.options.dopri5_max_steps)
                 out = u.t().unsqueeze(2).contiguous()               # [N, L, 1] like xnwan::xnode_forward
                 return out[:, 0, :] if (x.shape[1] == 1 and a_k) else out   # (src/model.py:89-91: [N, 1] on a single slice at T0)
             return L_norm(Xs, u_fn, self.p, lambda x: next(sols), volume, self.setup['N_r'])
@@ -467,6 +471,9 @@ class NODE_WAN_solver:
                       ('one packed upload + one gather launch per sample' if (not cube and eng.packed_load and not self.tabulate_on_host) else 'group by group'),
             'sub_steps': 'captured HIP graphs' if (cube and eng.use_graphs) else ('one C call per group sub-step (xw_substep_*)' if eng.use_runner and
                                                                                  eng.structure.c_kappa is not None else 'launch by launch'),
+            'ode_solver': ("dopri5 (adaptive, step sizes chosen on the device per group; its sub-steps run as eager launches, "
+                           "controllers read back every %d attempts)" % self.options.dopri5_chunk if eng.dopri5 else
+                           '%s (fixed grid: the sample times)' % self.config['solver']),
             'ranks': 1 if self.world is None else self.world.size,
             'exchange': None if self.world is None else ('xw_allreduce (RCCL) on the stream: inside the sub-step graphs / the group runner'
                                                          if self.world.capturable else 'torch.distributed, staged through the host'),
