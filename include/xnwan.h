@@ -118,6 +118,24 @@ typedef struct { const double* xT; const double* start; const double* Y; const d
 int xw_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
                      int method, int L, int d, int H, int K, int m, int mode, void* stream);
 
+/* ---- the TILED stepper family (csrc/xw_tiled.hip): fields wider than the two families above serve ---------------------
+ * u_hidden_dim H <= 256, u_hidden_hidden_dim K <= 256, u_layers 1..32, d + 2 <= 128, fixed-grid methods 0..2.  theta at the
+ * network's own widths (the generic layout), one wave per 16-path tile, every layer on v_mfma_f64_16x16x4.  Same jobs, outputs
+ * and slab format as xw_ode_fwd_multi / xw_ode_bwd_multi; in addition a WORKSPACE of xw_tiled_ode_work(...) doubles per 16-path
+ * tile of every job of the launch (jobs in order), owned by the caller and not read across launches.
+ *   xw_tiled_ode_ok       : 1 when (d, H, K, m) is served, else 0
+ *   xw_tiled_ode_work     : doubles of workspace per 16-path tile -- sweep = 0 for the forward pass, 1 for the sweep; XW_E_DIMS
+ *   xw_tiled_ode_bwd_slabs: number of parameter-gradient slabs a sweep of N paths writes
+ * The sweep recomputes its stages from the checkpoints Y; mode bits 0..2 and 5..6 as for xw_ode_bwd; bits 3 (adjoint) and 4
+ * (narrow tiles): XW_E_DIMS.  XwOdeFwdJob.act / act_x_only / narrow and XwOdeBwdJob.act are not read. */
+int xw_tiled_ode_ok(int d, int H, int K, int m);
+int xw_tiled_ode_work(int sweep, int d, int H, int K, int m);
+int xw_tiled_ode_bwd_slabs(int N);
+int xw_tiled_ode_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, const double* theta,
+                           int method, int L, int d, int H, int K, int m, double* zero16, double* work, void* stream);
+int xw_tiled_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
+                           int method, int L, int d, int H, int K, int m, int mode, double* work, void* stream);
+
 /* ---- solver 'dopri5': torchdiffeq's adaptive Dormand-Prince 5(4) (the default method of odeint, src/model.py:103-106) -----
  * One step size per JOB (= one odeint call of the reference: a group of paths), chosen on the device: every attempt is one
  * launch for all jobs, the last block of a job to finish it reduces the scaled error (RMS over N x Hn entries, Hn = the network's

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('XW_LIBRARY') or os.path.join(_HERE, 'libxnwan.so')   # (override: kernel experiments only)
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 c_f32p = ctypes.c_void_p   # coordinates / time grid: const double* (device)   [name kept from the float32 era]
 c_f64p = ctypes.c_void_p   # double*       (device)
@@ -71,6 +71,13 @@ SIGNATURES = {
     'xw_ode_bwd_slabs': [c_int],
     'xw_ode_act_rows': [c_int, c_int, c_int, c_int],
     'xw_ode_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
+    'xw_tiled_ode_ok': [c_int, c_int, c_int, c_int],
+    'xw_tiled_ode_work': [c_int, c_int, c_int, c_int, c_int],
+    'xw_tiled_ode_bwd_slabs': [c_int],
+    'xw_tiled_ode_fwd_multi': [ctypes.POINTER(XwOdeFwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p,
+                               c_f64p, c_vp],
+    'xw_tiled_ode_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_f64p, c_vp],
     'xw_dopri5_ctl_size': [],
     'xw_dopri5_work_size': [c_int],
     'xw_dopri5_init': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl,

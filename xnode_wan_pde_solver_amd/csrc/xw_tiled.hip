@@ -1,0 +1,514 @@
+// xw_tiled.hip -- the TILED stepper family: u_theta's forward pass and its reverse sweep at the network's own runtime widths,
+// u_hidden_dim H <= 256, u_hidden_hidden_dim K <= 256, u_layers 1..32, fixed-grid euler / midpoint / rk4 (3/8 rule).
+//
+// The fused kernels of xw_ode.hip keep a path tile's state and the field's weights in registers, sized at compile time, and stop
+// at (64, 16); the generic path (xw_generic.hip) runs one path per lane on the vector ALU and stops at the same widths.  Here
+// one wave owns a tile of 16 paths for every step of a job and runs every layer of the field as a [K_out x K_in] . [K_in x 16]
+// product on v_mfma_f64_16x16x4 (xw_common.h: "chain layout", features on the rows, the 16 paths on the columns), the widths
+// padded to multiples of 4 / 16 inside the kernel only.  Weights stream from global memory through L2 (at (128, 64, 8) the
+// field is ~46 k doubles, more than the LDS holds).  The tile's vectors -- state, stage inputs, layer activations -- live in a
+// per-tile slice of a caller-provided workspace (xw_tiled_ode_work), [rows][16] with the path innermost, so every phase
+// reads and writes whole 512-byte rows; the wave is its own workgroup and orders its phases with a barrier.
+//
+// The sweep recomputes each step's stages from the checkpoints Y (fixed grid: the steps are the sample times) and takes the
+// vector-Jacobian products; weight gradients are outer products over the tile's 16 paths on the same instruction (the paths are
+// its reduction dimension), added to the tile's slab of gslab[(N + 15) / 16][P_u] -- today's slab format, so k_slab_sum, the
+// all-reduce and Adam are unchanged.  Every slab entry is updated by one fixed lane of one wave in program order: no float
+// atomics, the same bits on every run and in a captured graph.  Lanes of a tile past the end of a job walk along with the last
+// path on a zero cotangent: they add exact zeros and store nothing.
+//
+// Parameters are read in the generic path's blob layout (u_offsets(d, H, K) at the network's own widths).
+// Not here: the continuous adjoint (mode bit 3), narrow tiles (mode bit 4), an activation store -- XW_E_DIMS.
+#include "xw_common.h"
+#include "xnwan.h"
+
+#define XWT_MAX_H 256
+#define XWT_MAX_K 256
+#define XWT_MAX_M 32
+
+namespace {
+
+// ---- the per-tile workspace: every vector is [rows][16] doubles -------------------------------------------------------------
+struct TileWork {
+  long xt, xp, zs, th, dz, dzp, hv, ub, st, total;   // (offsets in doubles; hv: the first of nh H-vectors)
+  int nh;
+};
+__host__ __device__ inline TileWork tile_work(int sweep, int d, int H, int K, int m) {
+  TileWork w;
+  long p = 0;
+  const int nz = sweep ? m : 2;                      // forward: two K-vectors in turn; sweep: every layer's pre-activation
+  w.xt = p; p += 32L * d;                            // x of the 16 paths (sweep: then d/dx of them)
+  w.xp = p; p += 16L * K;                            // Win[:, 0..d) x + Win.b (hoisted: x does not move along a path)
+  w.zs = p; p += 16L * K * nz;
+  w.th = p; p += 16L * K;                            // tanh of the last pre-activation
+  w.dz = p; p += 16L * K;                            // (sweep) cotangents of a layer's pre-activation, ...
+  w.dzp = p; p += 16L * K;                           //   ... of the one below, and Sx: the summed cotangent of z_0
+  w.nh = sweep ? 12 : 5;
+  w.hv = p; p += 16L * H * w.nh;
+  w.ub = p; p += 16;                                 // cotangent on u of the current time index
+  w.st = p; p += 16;                                 // start values
+  p += 16L * K;                                      // (sweep: Sx)
+  w.total = p;
+  return w;
+}
+
+__device__ __forceinline__ int lane_id() { return threadIdx.x; }
+__device__ __forceinline__ void sync_tile() { __syncthreads(); }   // one wave per workgroup: orders the phases' global traffic
+
+enum { A_PLAIN = 0, A_RELU = 1 };
+enum { E_NONE = 0, E_TANH_D = 1, E_GATE = 2 };
+
+// out[r][p] = init(r, p) + sum_c W(r, c) A[c][p],  r < R, c < C;  W(r, c) = W[r wr + c wc] (so transposed products are the same
+// loop), A gated by relu when aop == A_RELU; init = bias[r] (may be null) + tcol[r] * t (may be null) + add[r][p] (may be null);
+// epilogue E_TANH_D: times (1 - g^2) with g = aux[r][p] (tanh values), E_GATE: zero where aux[r][p] <= 0.
+// MFMA: A-operand W(r0 + (l & 15), c0 + (l >> 4)), B-operand A[c0 + (l >> 4)][l & 15]; D row r0 + (l >> 4) + 4 i, column l & 15.
+__device__ void tgemm(const double* __restrict__ W, long wr, long wc, int R, int C, const double* A, int aop, const double* bias,
+                      const double* tcol, long tcs, double t, const double* add, int eop, const double* aux, double* out) {
+  const int l = lane_id(), lr = l & 15, lk = l >> 4;
+  for (int r0 = 0; r0 < R; r0 += 16) {
+    const int ra = r0 + lr;
+    const bool rok = ra < R;
+    const double* wrow = W + (long)(rok ? ra : 0) * wr;
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      const int c = c0 + lk;
+      const bool cok = c < C;
+      const double wa = (rok && cok) ? wrow[(long)c * wc] : 0.0;
+      double b = cok ? A[c * 16 + lr] : 0.0;
+      if (aop == A_RELU) b = b > 0.0 ? b : 0.0;
+      acc = XW_MFMA(wa, b, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = r0 + lk + 4 * i;
+      if (r >= R) continue;
+      const int e = r * 16 + lr;
+      double v = acc[i];
+      if (bias) v += bias[r];
+      if (tcol) v = fma(tcol[(long)r * tcs], t, v);
+      if (add) v += add[e];
+      if (eop == E_TANH_D) v *= 1.0 - aux[e] * aux[e];
+      else if (eop == E_GATE) v = aux[e] > 0.0 ? v : 0.0;
+      out[e] = v;
+    }
+  }
+  sync_tile();
+}
+
+// slab[e0 + r ld + c] += sum_p U[r][p] V[c][p] (V gated by relu when vop == A_RELU), r < R, c < C: the 16 paths are the
+// reduction dimension (four k-steps).  A-operand U[r0 + (l & 15)][k], B-operand V[c0 + (l & 15)][k], k = 4 s + (l >> 4);
+// entry (r0 + (l >> 4) + 4 i, c0 + (l & 15)) belongs to one lane, always the same one.
+__device__ void touter(double* slab, long e0, int ld, int R, int C, const double* U, const double* V, int vop) {
+  const int l = lane_id(), lr = l & 15, lk = l >> 4;
+  for (int r0 = 0; r0 < R; r0 += 16) {
+    const int ra = r0 + lr;
+    double ua[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) ua[s] = ra < R ? U[ra * 16 + 4 * s + lk] : 0.0;
+    for (int c0 = 0; c0 < C; c0 += 16) {
+      const int ca = c0 + lr;
+      d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        double v = ca < C ? V[ca * 16 + 4 * s + lk] : 0.0;
+        if (vop == A_RELU) v = v > 0.0 ? v : 0.0;
+        acc = XW_MFMA(ua[s], v, acc);
+      }
+      const int c = c0 + lr;
+      if (c < C) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = r0 + lk + 4 * i;
+          if (r < R) slab[e0 + (long)r * ld + c] += acc[i];
+        }
+      }
+    }
+  }
+}
+
+// slab[e0 + r stride] += scale sum_p U[r][p] (w ? w[p] : 1), r < R -- bias gradients and the like; paths summed in order
+__device__ void trowsum(double* slab, long e0, long stride, int R, const double* U, const double* w, double scale) {
+  for (int r = lane_id(); r < R; r += 64) {
+    double s = 0.0;
+    for (int p = 0; p < 16; ++p) s = w ? fma(U[r * 16 + p], w[p], s) : s + U[r * 16 + p];
+    slab[e0 + (long)r * stride] += scale * s;
+  }
+}
+
+struct Net {
+  const double* th;
+  UOff o;
+  int d, H, K, m;
+};
+
+// fo = F(t, yin) for the tile (src/model.py:130-141, 153-156); the pre-activations land in zs (the forward: two K-vectors in
+// turn, zs_all == false; the sweep: layer l at zs + 16 K l) and tanh(z_{m-1}) in th
+__device__ void tfield(const Net& n, const TileWork& w, double* ws, double t, const double* yin, double* fo, bool zs_all) {
+  const int K = n.K, H = n.H, ld = n.o.ldin;
+  const double* th = n.th;
+  double* zs = ws + w.zs;
+  // z_0 = Win[:, d+1:] y + Win[:, d] t + xproj
+  tgemm(th + n.o.Win + n.d + 1, ld, 1, K, H, yin, A_PLAIN, nullptr, th + n.o.Win + n.d, ld, t, ws + w.xp, E_NONE, nullptr, zs);
+  double* z = zs;
+  for (int l = 1; l < n.m; ++l) {
+    double* zn = zs_all ? zs + 16L * K * l : zs + 16L * K * (l & 1);
+    tgemm(th + n.o.Wh, K, 1, K, K, z, A_RELU, th + n.o.Whb, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, zn);
+    z = zn;
+  }
+  double* tz = ws + w.th;
+  for (int e = lane_id(); e < 16 * K; e += 64) tz[e] = xw_tanh(z[e]);
+  sync_tile();
+  if (fo) tgemm(th + n.o.Wo, K, 1, H, K, tz, A_PLAIN, th + n.o.Wob, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, fo);
+}
+
+// a^T dF/d(y, theta) at (t, yin): gy (overwritten), Sx += cotangent of z_0, parameter gradients into slab (or none)
+__device__ void tfield_vjp(const Net& n, const TileWork& w, double* ws, double t, const double* yin, const double* a, double* gy,
+                           double* slab) {
+  const int K = n.K, H = n.H, ld = n.o.ldin;
+  const double* th = n.th;
+  tfield(n, w, ws, t, yin, nullptr, true);
+  const double* zs = ws + w.zs;
+  const double* tz = ws + w.th;
+  double* dz = ws + w.dz;
+  double* dzp = ws + w.dzp;
+  double* Sx = ws + w.total - 16L * K;
+  // dz = (Wo^T a) (1 - tanh^2)
+  tgemm(th + n.o.Wo, 1, K, K, H, a, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_TANH_D, tz, dz);
+  if (slab) {
+    touter(slab, n.o.Wo, K, H, K, a, tz, A_PLAIN);
+    trowsum(slab, n.o.Wob, 1, H, a, nullptr, 1.0);
+  }
+  for (int l = n.m - 1; l >= 1; --l) {
+    const double* zp = zs + 16L * K * (l - 1);
+    if (slab) {
+      touter(slab, n.o.Wh, K, K, K, dz, zp, A_RELU);
+      trowsum(slab, n.o.Whb, 1, K, dz, nullptr, 1.0);
+    }
+    tgemm(th + n.o.Wh, 1, K, K, K, dz, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, zp, dzp);
+    double* s_ = dz; dz = dzp; dzp = s_;
+  }
+  if (slab) {
+    touter(slab, (long)n.o.Win + n.d + 1, ld, K, H, dz, yin, A_PLAIN);
+    trowsum(slab, (long)n.o.Win + n.d, ld, K, dz, nullptr, t);
+  }
+  for (int e = lane_id(); e < 16 * K; e += 64) Sx[e] += dz[e];
+  // gy = Win[:, d+1:]^T dz
+  tgemm(th + n.o.Win + n.d + 1, 1, ld, H, K, dz, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gy);
+}
+
+// the tile's x (clamped to the last path past the end) and xproj = Win[:, 0..d) x + Win.b
+__device__ void tile_x(const Net& n, const TileWork& w, double* ws, const double* xT, int N, int p0) {
+  double* xt = ws + w.xt;
+  for (int e = lane_id(); e < 16 * n.d; e += 64) {
+    const int p = p0 + (e & 15);
+    xt[e] = xT[(long)(e >> 4) * N + (p < N ? p : N - 1)];
+  }
+  sync_tile();
+  tgemm(n.th + n.o.Win, n.o.ldin, 1, n.K, n.d, xt, A_PLAIN, n.th + n.o.Winb, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, ws + w.xp);
+}
+
+// y0 = IL(start) (src/model.py:78,97): pre0 = IL0 s, pre2 = IL2 relu(pre0), y = IL4 relu(pre2)
+__device__ void tlift(const Net& n, const double* st, double* pre0, double* pre2, double* y) {
+  const int H = n.H;
+  const double* th = n.th;
+  for (int e = lane_id(); e < 16 * H; e += 64) pre0[e] = fma(th[n.o.IL0w + (e >> 4)], st[e & 15], th[n.o.IL0b + (e >> 4)]);
+  sync_tile();
+  tgemm(th + n.o.IL2w, H, 1, H, H, pre0, A_RELU, th + n.o.IL2b, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, pre2);
+  tgemm(th + n.o.IL4w, H, 1, H, H, pre2, A_RELU, th + n.o.IL4b, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, y);
+}
+
+// dst = src0 + c1 src1 (+ c2 src2 (+ c3 src3)) elementwise over an H-vector (null sources are skipped)
+__device__ void tcomb(int H, double* dst, const double* s0, double c1, const double* s1, double c2 = 0.0, const double* s2 = nullptr,
+                      double c3 = 0.0, const double* s3 = nullptr) {
+  for (int e = lane_id(); e < 16 * H; e += 64) {
+    double v = s0 ? s0[e] : 0.0;
+    v = fma(c1, s1[e], v);
+    if (s2) v = fma(c2, s2[e], v);
+    if (s3) v = fma(c3, s3[e], v);
+    dst[e] = v;
+  }
+  sync_tile();
+}
+
+__device__ __forceinline__ void set_prio(int drop) {
+  switch (3 - (drop & 3)) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+  }
+}
+
+__global__ void __launch_bounds__(64) kt_ode_fwd(XwOdeFwdJob job, const double* __restrict__ tf, const double* __restrict__ theta,
+                                                  int method, int L, int d, int H, int K, int m, double* __restrict__ work) {
+  set_prio(job.prio_drop);
+  const int N = job.N, p0 = blockIdx.x * 16;
+  const Net n = {theta, u_offsets(d, H, K), d, H, K, m};
+  const TileWork w = tile_work(0, d, H, K, m);
+  double* ws = work + (long)blockIdx.x * w.total;
+  double* y = ws + w.hv;
+  double* acc = y + 16L * H;
+  double* cc = acc + 16L * H;
+  double* tmp = cc + 16L * H;
+  double* fo = tmp + 16L * H;
+  double* st = ws + w.st;
+  const int l16 = lane_id() & 15;
+  if (lane_id() < 16) st[l16] = job.start[p0 + l16 < N ? p0 + l16 : N - 1];
+  tile_x(n, w, ws, job.xT, N, p0);
+  tlift(n, st, acc, cc, y);
+  const double* flw = theta + n.o.FLw;
+  for (int l = 0; l < L; ++l) {
+    if (l > 0) {
+      const double t0 = tf[l - 1], dt = tf[l] - tf[l - 1];
+      if (method == 0) {
+        tfield(n, w, ws, t0, y, fo, false);
+        tcomb(H, y, y, dt, fo);
+      } else if (method == 1) {
+        tfield(n, w, ws, t0, y, fo, false);
+        tcomb(H, tmp, y, dt / 2, fo);
+        tfield(n, w, ws, t0 + dt / 2, tmp, fo, false);
+        tcomb(H, y, y, dt, fo);
+      } else {                                                   // 3/8 rule: acc = k1 + 3 k2 + 3 k3 + k4, cc = k1 - k2
+        tfield(n, w, ws, t0, y, fo, false);
+        tcomb(H, acc, nullptr, 1.0, fo);
+        tcomb(H, cc, nullptr, 1.0, fo);
+        tcomb(H, tmp, y, dt / 3, fo);
+        tfield(n, w, ws, t0 + dt / 3, tmp, fo, false);
+        tcomb(H, acc, acc, 3.0, fo);
+        tcomb(H, tmp, y, dt, fo, -dt / 3, cc);
+        tcomb(H, cc, cc, -1.0, fo);
+        tfield(n, w, ws, t0 + 2 * dt / 3, tmp, fo, false);
+        tcomb(H, acc, acc, 3.0, fo);
+        tcomb(H, tmp, y, dt, cc, dt, fo);
+        tfield(n, w, ws, t0 + dt, tmp, fo, false);
+        tcomb(H, acc, acc, 1.0, fo);
+        tcomb(H, y, y, dt / 8, acc);
+      }
+    }
+    if (lane_id() < 16 && p0 + l16 < N) {
+      double u = theta[n.o.FLb];
+      for (int j = 0; j < H; ++j) u = fma(flw[j], y[j * 16 + l16], u);
+      job.u[(long)l * N + p0 + l16] = u;
+    }
+    if (job.Y)
+      for (int e = lane_id(); e < 16 * H; e += 64)
+        if (p0 + (e & 15) < N) job.Y[((long)l * H + (e >> 4)) * N + p0 + (e & 15)] = y[e];
+  }
+}
+
+#include "xw_generic_cot.h"
+
+__global__ void __launch_bounds__(64) kt_ode_bwd(XwOdeBwdJob job, const double* __restrict__ tf, const double* __restrict__ theta,
+                                                  int method, int L, int d, int H, int K, int m, int mode, double* __restrict__ work) {
+  set_prio(mode >> 5);
+  const int N = job.N, p0 = blockIdx.x * 16;
+  const bool want_x = (mode & 1) != 0, ones_x = (mode & 4) != 0;
+  double* slab = (mode & 2) ? job.gslab + (long)blockIdx.x * u_offsets(d, H, K).total : nullptr;
+  const Net n = {theta, u_offsets(d, H, K), d, H, K, m};
+  const TileWork w = tile_work(1, d, H, K, m);
+  double* ws = work + (long)blockIdx.x * w.total;
+  double* hv = ws + w.hv;
+  double* lam = hv;
+  double* Y1 = hv + 16L * H * 1;
+  double* Y2 = hv + 16L * H * 2;
+  double* Y3 = hv + 16L * H * 3;
+  double* Y4 = hv + 16L * H * 4;
+  double* cc = hv + 16L * H * 5;
+  double* fo = hv + 16L * H * 6;
+  double* g4 = hv + 16L * H * 7;
+  double* g3 = hv + 16L * H * 8;
+  double* g2 = hv + 16L * H * 9;
+  double* a = hv + 16L * H * 10;
+  double* gy = hv + 16L * H * 11;
+  double* ub = ws + w.ub;
+  double* st = ws + w.st;
+  double* Sx = ws + w.total - 16L * K;
+  const int l16 = lane_id() & 15;
+  const bool lane_active = p0 + l16 < N;
+  if (lane_id() < 16) st[l16] = job.start[lane_active ? p0 + l16 : N - 1];
+  for (int e = lane_id(); e < 16 * K; e += 64) Sx[e] = 0.0;
+  for (int e = lane_id(); e < 16 * H; e += 64) lam[e] = 0.0;
+  tile_x(n, w, ws, job.xT, N, p0);
+  const double* flw = theta + n.o.FLw;
+  for (int l = L - 1; l >= 1; --l) {
+    if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, l, L, p0 + l16) : 0.0;
+    for (int e = lane_id(); e < 16 * H; e += 64) {
+      const int p = p0 + (e & 15);
+      Y1[e] = job.Y[((long)(l - 1) * H + (e >> 4)) * N + (p < N ? p : N - 1)];
+      Y2[e] = job.Y[((long)l * H + (e >> 4)) * N + (p < N ? p : N - 1)];      // (y_l, for the read-out's gradient)
+    }
+    sync_tile();
+    for (int e = lane_id(); e < 16 * H; e += 64) lam[e] = fma(flw[e >> 4], ub[e & 15], lam[e]);
+    if (slab) {
+      trowsum(slab, n.o.FLw, 1, H, Y2, ub, 1.0);
+      if (lane_id() == 0) {
+        double s = 0.0;
+        for (int p = 0; p < 16; ++p) s += ub[p];
+        slab[n.o.FLb] += s;
+      }
+    }
+    sync_tile();
+    // y_l = step(y_{l-1}): lam becomes the cotangent of y_{l-1}
+    const double t0 = tf[l - 1], dt = tf[l] - tf[l - 1];
+    if (method == 0) {
+      tcomb(H, a, nullptr, dt, lam);
+      tfield_vjp(n, w, ws, t0, Y1, a, gy, slab);
+      tcomb(H, lam, lam, 1.0, gy);
+    } else if (method == 1) {
+      tfield(n, w, ws, t0, Y1, fo, true);
+      tcomb(H, Y2, Y1, dt / 2, fo);
+      tcomb(H, a, nullptr, dt, lam);
+      tfield_vjp(n, w, ws, t0 + dt / 2, Y2, a, gy, slab);
+      tcomb(H, lam, lam, 1.0, gy);
+      tcomb(H, a, nullptr, dt / 2, gy);
+      tfield_vjp(n, w, ws, t0, Y1, a, gy, slab);
+      tcomb(H, lam, lam, 1.0, gy);
+    } else {
+      tfield(n, w, ws, t0, Y1, fo, true);                        // k1; cc = k1
+      tcomb(H, cc, nullptr, 1.0, fo);
+      tcomb(H, Y2, Y1, dt / 3, fo);
+      tfield(n, w, ws, t0 + dt / 3, Y2, fo, true);               // k2
+      tcomb(H, Y3, Y1, dt, fo, -dt / 3, cc);
+      tcomb(H, cc, cc, -1.0, fo);                                // cc = k1 - k2
+      tfield(n, w, ws, t0 + 2 * dt / 3, Y3, fo, true);           // k3
+      tcomb(H, Y4, Y1, dt, cc, dt, fo);
+      tcomb(H, a, nullptr, dt / 8, lam);
+      tfield_vjp(n, w, ws, t0 + dt, Y4, a, g4, slab);
+      tcomb(H, a, nullptr, 3 * dt / 8, lam, dt, g4);
+      tfield_vjp(n, w, ws, t0 + 2 * dt / 3, Y3, a, g3, slab);
+      tcomb(H, a, nullptr, 3 * dt / 8, lam, -dt, g4, dt, g3);
+      tfield_vjp(n, w, ws, t0 + dt / 3, Y2, a, g2, slab);
+      for (int e = lane_id(); e < 16 * H; e += 64) a[e] = (dt / 8) * lam[e] + dt * g4[e] - (dt / 3) * g3[e] + (dt / 3) * g2[e];
+      sync_tile();
+      tfield_vjp(n, w, ws, t0, Y1, a, gy, slab);
+      for (int e = lane_id(); e < 16 * H; e += 64) lam[e] += g4[e] + g3[e] + g2[e] + gy[e];
+      sync_tile();
+    }
+  }
+  // l = 0: read-out, then the lift 1 -> H -> H -> H; with mode bit 2 the x-side outputs are those of the ALL-ONES cotangent
+  // while the parameter gradients use the job's own (xw_generic.hip kg_ode_bwd)
+  if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, 0, L, p0 + l16) : 0.0;
+  sync_tile();
+  double* p0v = Y2;
+  double* p2v = Y3;
+  double* y0 = Y4;
+  double* l0 = cc;
+  double* dh2 = fo;
+  double* dh1 = g4;
+  tlift(n, st, p0v, p2v, y0);
+  if (slab) {
+    trowsum(slab, n.o.FLw, 1, H, y0, ub, 1.0);
+    if (lane_id() == 0) {
+      double s = 0.0;
+      for (int p = 0; p < 16; ++p) s += ub[p];
+      slab[n.o.FLb] += s;
+    }
+  }
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 0 && !slab) continue;
+    if (pass == 1 && !(want_x && job.gs != nullptr)) continue;
+    const bool ones = pass == 1 && ones_x;
+    for (int e = lane_id(); e < 16 * H; e += 64) l0[e] = fma(flw[e >> 4], ones ? 1.0 : ub[e & 15], lam[e]);
+    sync_tile();
+    tgemm(theta + n.o.IL4w, 1, H, H, H, l0, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p2v, dh2);
+    tgemm(theta + n.o.IL2w, 1, H, H, H, dh2, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p0v, dh1);
+    if (pass == 0) {
+      touter(slab, n.o.IL4w, H, H, H, l0, p2v, A_RELU);
+      touter(slab, n.o.IL2w, H, H, H, dh2, p0v, A_RELU);
+      trowsum(slab, n.o.IL4b, 1, H, l0, nullptr, 1.0);
+      trowsum(slab, n.o.IL2b, 1, H, dh2, nullptr, 1.0);
+      trowsum(slab, n.o.IL0w, 1, H, dh1, st, 1.0);
+      trowsum(slab, n.o.IL0b, 1, H, dh1, nullptr, 1.0);
+      sync_tile();
+    } else if (lane_id() < 16 && lane_active) {
+      double s = 0.0;
+      for (int i = 0; i < H; ++i) s = fma(theta[n.o.IL0w + i], dh1[i * 16 + l16], s);
+      job.gs[p0 + l16] = s;
+    }
+  }
+  // the x columns and the bias of the input layer, from the summed cotangent of its pre-activation
+  if (slab) {
+    trowsum(slab, n.o.Winb, 1, K, Sx, nullptr, 1.0);
+    touter(slab, n.o.Win, n.o.ldin, K, d, Sx, ws + w.xt, A_PLAIN);
+  }
+  if (want_x && job.gx != nullptr) {
+    double* gxt = ws + w.xt + 16L * d;
+    tgemm(theta + n.o.Win, 1, n.o.ldin, d, K, Sx, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gxt);
+    for (int e = lane_id(); e < 16 * d; e += 64)
+      if (p0 + (e & 15) < N) job.gx[(long)(e >> 4) * N + p0 + (e & 15)] = gxt[e];
+  }
+}
+
+}  // namespace
+
+// ---- entry points (include/xnwan.h) -------------------------------------------------------------------------------------------
+extern "C" int xw_tiled_ode_ok(int d, int H, int K, int m) {
+  return H >= 1 && H <= XWT_MAX_H && K >= 1 && K <= XWT_MAX_K && m >= 1 && m <= XWT_MAX_M && d >= 1 && d + 2 <= 128;
+}
+
+extern "C" int xw_tiled_ode_work(int sweep, int d, int H, int K, int m) {
+  if (!xw_tiled_ode_ok(d, H, K, m)) return XW_E_DIMS;
+  return (int)tile_work(sweep != 0, d, H, K, m).total;
+}
+
+extern "C" int xw_tiled_ode_bwd_slabs(int N) { return (N + 15) / 16; }
+
+static int check_common(int njobs, const double* t, const double* theta, int method, int L, int d, int H, int K, int m,
+                        const double* work) {
+  if (njobs < 1 || !t || !theta || !work || L < 1 || method < 0 || method > 2) return XW_E_ARG;
+  if (!xw_tiled_ode_ok(d, H, K, m)) return XW_E_DIMS;
+  return 0;
+}
+
+extern "C" int xw_tiled_ode_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, const double* theta, int method, int L,
+                                      int d, int H, int K, int m, double* zero16, double* work, void* stream) {
+  if (!jobs) return XW_E_ARG;
+  const int c = check_common(njobs, t, theta, method, L, d, H, K, m, work);
+  if (c) return c;
+  hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < njobs; ++i)
+    if (!jobs[i].xT || !jobs[i].start || !jobs[i].u || jobs[i].N < 1) return XW_E_ARG;
+  if (zero16 != nullptr) {
+    const hipError_t e = hipMemsetAsync(zero16, 0, 16 * sizeof(double), s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const long per = tile_work(0, d, H, K, m).total;
+  long off = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const int tiles = (jobs[i].N + 15) / 16;
+    hipLaunchKernelGGL(kt_ode_fwd, dim3(tiles), dim3(64), 0, s, jobs[i], t, theta, method, L, d, H, K, m, work + off);
+    off += per * tiles;
+  }
+  return xw_launch_status();
+}
+
+extern "C" int xw_tiled_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta, int method, int L,
+                                      int d, int H, int K, int m, int mode, double* work, void* stream) {
+  if (!jobs || (mode & 3) == 0) return XW_E_ARG;
+  const int c = check_common(njobs, t, theta, method, L, d, H, K, m, work);
+  if (c) return c;
+  if (mode & (8 | 16)) return XW_E_DIMS;                  // (no continuous adjoint, no narrow tiles in this family)
+  if ((mode & 4) && (mode & 3) != 3) return XW_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = u_offsets(d, H, K).total;
+  for (int i = 0; i < njobs; ++i) {
+    const XwOdeBwdJob& j = jobs[i];
+    if (!j.xT || !j.start || !j.Y || j.N < 1) return XW_E_ARG;
+    if (j.res_u != nullptr && j.ubar != nullptr) return XW_E_ARG;
+    if ((mode & 2) && !j.gslab) return XW_E_ARG;
+    if ((mode & 1) && !(mode & 4) && (!j.gx || !j.gs)) return XW_E_ARG;
+  }
+  const long per = tile_work(1, d, H, K, m).total;
+  long off = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const XwOdeBwdJob& j = jobs[i];
+    const int tiles = (j.N + 15) / 16;
+    if (mode & 2) {
+      const hipError_t e = hipMemsetAsync(j.gslab, 0, sizeof(double) * P * tiles, s);
+      if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kt_ode_bwd, dim3(tiles), dim3(64), 0, s, j, t, theta, method, L, d, H, K, m, mode, work + off);
+    off += per * tiles;
+  }
+  return xw_launch_status();
+}

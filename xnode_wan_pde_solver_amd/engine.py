@@ -194,7 +194,24 @@ class Engine:
         self.W, self.q = v_mod.kwidth, config['v_layers']
         # widths beyond the MFMA containers run on the generic path (csrc/xw_generic.hip): correct, deterministic, and two to three
         # orders of magnitude slower -- said once, loudly
-        self.generic = (KN.ode_generic(self.H, self.K, self.m), KN.disc_generic(self.W))
+        # the stepper family (kernels.stepper_family): the fused MFMA containers, the generic path or the tiled family
+        # (csrc/xw_tiled.hip: any width up to 256 at the network's own widths, fixed grid; EngineOptions.tiled_stepper)
+        self.stepper = KN.stepper_family(config['u_hidden_dim'], config['u_hidden_hidden_dim'], self.m, opt.tiled_stepper)
+        self.tiled = self.stepper == 'tiled'
+        if self.tiled:
+            if (self.H, self.K) != (config['u_hidden_dim'], config['u_hidden_hidden_dim']):
+                raise XnwanError('the tiled stepper family reads theta at the network\'s own widths; the module was bound at %s'
+                                 % ((self.H, self.K),))
+            if self.adjoint:
+                raise XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
+                                 'u_hidden_hidden_dim = %d, u_layers = %d: it reverses the steps taken; the continuous adjoint exists '
+                                 'for the MFMA containers %s, u_layers <= %d)' % (self.H, self.K, self.m, KN.ODE_WIDTHS, KN.ODE_MAX_DEPTH))
+            if self.dopri5:
+                raise XnwanError("solver 'dopri5' is not served by the tiled stepper family (u_hidden_dim = %d, u_hidden_hidden_dim = %d, "
+                                 "u_layers = %d): its field code is the generic path's, up to %s and u_layers %d; the tiled family runs "
+                                 "the fixed-grid solvers %s" % (self.H, self.K, self.m, KN.GENERIC_ODE_MAX, KN.GENERIC_ODE_MAX_DEPTH,
+                                                                sorted(KN.METHODS)))
+        self.generic = (self.stepper == 'generic', KN.disc_generic(self.W))
         if any(self.generic):
             import warnings
             which = ' and '.join(n_ for n_, g_ in zip(('u_theta (u_hidden_dim %d, u_hidden_hidden_dim %d, u_layers %d)' % (self.H, self.K, self.m),
@@ -295,6 +312,11 @@ class Engine:
         self.use_runner = opt.use_runner      # one C call per eager group sub-step (xw_substep_*)
         if self.dopri5:
             self.use_graphs = self.use_streams = self.use_runner = self.keep_activations = False
+        if self.tiled:
+            # the group runner (xw_substep_*) is fused fixed-family C; the tiled sweeps recompute from Y (no activation store) and
+            # have no narrow tiles.  Graphs and streams stay on.
+            self.use_runner = self.keep_activations = False
+            self.narrow = '0'
         # Measured (profiles/r04_shard_sweep.md): forward and the sweep without weight gradients gain on shards up to ~2048
         # paths (0.302 -> 0.272 ms per sub-step at 512 paths, 0.332 -> 0.294 at 1024, 0.375 -> 0.367 at 2048); the narrow sweep
         # WITH weight gradients only ties the two-wave duo sweep (88 against 83 us alone) and is left to XW_NARROW_SET=fxp; at
@@ -1602,6 +1624,8 @@ class Engine:
     def _ode_fwd_multi(self, jobs, t, th, method, H, K, m, zero16=None, **kw):
         """KN.ode_fwd_multi; with dopri5 one kernels.dopri5_fwd per 8 jobs, each job's step record kept for its sweep
         (keyed by the job's sample and grid, which the sweep jobs share)"""
+        if self.tiled:
+            return KN.tiled_ode_fwd_multi(jobs, t, th, method, H, K, m, zero16=zero16, **kw)
         if method != KN.DOPRI5:
             return KN.ode_fwd_multi(jobs, t, th, method, H, K, m, zero16=zero16, **kw)
         if zero16 is not None:
@@ -1616,6 +1640,8 @@ class Engine:
 
     def _ode_bwd_multi(self, jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, **kw):
         """KN.ode_bwd_multi; with dopri5 kernels.dopri5_sweep over the records of the forward that produced these jobs' u"""
+        if self.tiled:
+            return KN.tiled_ode_bwd_multi(jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint, **kw)
         if method != KN.DOPRI5:
             return KN.ode_bwd_multi(jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint, **kw)
         for i in range(0, len(jobs), KN.DOPRI5_MAXJOBS):
@@ -1623,6 +1649,8 @@ class Engine:
             KN.dopri5_sweep(part, t, th, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones)
 
     def _u_forward(self, xT, t, start):
+        if self.tiled:
+            return KN.tiled_ode_fwd(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, want_Y=False)[0]
         return KN.u_forward(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, self.config['u_hidden_dim'],
                             chunk=self.options.dopri5_chunk, max_steps=self.options.dopri5_max_steps)
 

@@ -103,6 +103,35 @@ def ode_generic(H, K, m=1):
     return (H, K) not in ODE_WIDTHS or m > (ODE_WIDE_MAX_DEPTH if (H, K) == ODE_WIDTHS[-1] else ODE_MAX_DEPTH)
 
 
+TILED_ODE_MAX = (256, 256)                 # csrc/xw_tiled.hip: the tiled family, at the network's own widths, depths up to
+TILED_ODE_MAX_DEPTH = 32                   # this, fixed-grid methods only
+TILED_POLICIES = ('beyond', 'generic')     # EngineOptions.tiled_stepper
+
+
+def stepper_family(H, K, m=1, policy='beyond'):
+    """which stepper family runs a (u_hidden_dim H, u_hidden_hidden_dim K, u_layers m) field: 'mfma' (the fused containers),
+    'generic' (csrc/xw_generic.hip) or 'tiled' (csrc/xw_tiled.hip).  policy 'beyond': the tiled family only where the other two
+    refuse; 'generic': also in place of the generic path."""
+    if policy not in TILED_POLICIES:
+        raise XnwanError('tiled_stepper = %r: one of %s' % (policy, TILED_POLICIES))
+    if not (1 <= H <= TILED_ODE_MAX[0] and 1 <= K <= TILED_ODE_MAX[1] and 1 <= m <= TILED_ODE_MAX_DEPTH):
+        raise XnwanError('u_hidden_dim = %d, u_hidden_hidden_dim = %d, u_layers = %d: the stepper kernels serve widths up to %s (MFMA) / '
+                         '%s (generic path) / %s (tiled), depths up to %d / %d / %d'
+                         % (H, K, m, ODE_WIDTHS[-1], GENERIC_ODE_MAX, TILED_ODE_MAX, ODE_MAX_DEPTH, GENERIC_ODE_MAX_DEPTH, TILED_ODE_MAX_DEPTH))
+    try:
+        Hc, Kc = ode_container(H, K, m)
+    except XnwanError:
+        return 'tiled'
+    if not ode_generic(Hc, Kc, m):
+        return 'mfma'
+    return 'tiled' if policy == 'generic' else 'generic'
+
+
+def stepper_kdims(H, K, m=1, policy='beyond'):
+    """the widths the parameter blob is laid out at: the MFMA container, or the network's own (generic, tiled)"""
+    return ode_container(H, K, m) if stepper_family(H, K, m, policy) != 'tiled' else (H, K)
+
+
 def disc_container(W):
     for Wc in DISC_WIDTHS:
         if W <= Wc and lib.xw_disc_act_rows(Wc, 1) >= 0:
@@ -236,6 +265,93 @@ def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_on
         raise XnwanError('narrow-tile sweeps run from the activation store of euler / midpoint (no adjoint=True, no rk4)')
     mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | (8 if adjoint else 0) | (16 if narrow else 0) | ((int(prio_drop) & 3) << 5)
     check(lib.xw_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _stream()), 'xw_ode_bwd_multi')
+
+
+def tiled_ode_work(sweep, d, H, K, m, tiles, dev):
+    """the workspace of one tiled launch over `tiles` 16-path tiles (csrc/xw_tiled.hip: per-tile vectors)"""
+    per = lib.xw_tiled_ode_work(1 if sweep else 0, d, H, K, m)
+    check(min(per, 0), 'xw_tiled_ode_work')
+    return torch.empty(per * tiles, dtype=F64, device=dev)
+
+
+def tiled_ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, prio_drop=0, **_hints):
+    """ode_fwd_multi on the tiled family (csrc/xw_tiled.hip): jobs as there (act, act_x_only and narrow are hints the family
+    does not take: no activation store, no narrow tiles); theta at the network's own widths"""
+    _need_gpu()
+    L = t.shape[0]
+    d = jobs[0]['xT'].shape[0]
+    _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('the tiled stepper family runs the fixed-grid methods %s only' % sorted(METHODS))
+    arr = (XwOdeFwdJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
+        _chk(j.get('Y'), F64, (L, H, N), 'Y')
+        a.xT, a.start, a.u, a.Y, a.act, a.N = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y')), 0, N
+        a.act_x_only, a.narrow, a.prio_drop = 0, 0, int(prio_drop)
+    _chk(zero16, F64, (16,), 'zero16')
+    work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device)
+    check(lib.xw_tiled_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _p(work), _stream()),
+          'xw_tiled_ode_fwd_multi')
+
+
+def tiled_ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False,
+                        prio_drop=0):
+    """ode_bwd_multi on the tiled family: the same jobs (stored cotangent or residual form), outputs and slab format; the sweep
+    recomputes from the checkpoints Y.  No continuous adjoint, no narrow tiles."""
+    _need_gpu()
+    if adjoint:
+        raise XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
+                         'u_hidden_hidden_dim = %d): it reverses the steps taken' % (H, K))
+    if narrow:
+        raise XnwanError('narrow tiles are not served by the tiled stepper family')
+    if x_cot_ones and not (want_x and want_params):
+        raise XnwanError('x_cot_ones needs want_x and want_params')
+    if not (want_x or want_params):
+        raise XnwanError('a sweep produces x outputs, parameter gradients or both')
+    L = t.shape[0]
+    d = jobs[0]['xT'].shape[0]
+    P = theta_size(d, H, K)
+    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    arr = (XwOdeBwdJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['Y'], F64, (L, H, N), 'Y')
+        _chk(j.get('ubar'), F64, (L, N), 'ubar')
+        if want_x and not (x_cot_ones and j.get('gx') is None):
+            _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
+        if want_params:
+            _chk(j['gslab'], F64, (lib.xw_tiled_ode_bwd_slabs(N), P), 'gslab')
+        a.xT, a.start, a.Y, a.ubar, a.N, a.act = _p(j['xT']), _p(j['start']), _p(j['Y']), _p(j.get('ubar')), N, 0
+        a.gx, a.gs, a.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
+        _set_res(a, j, L, N)
+    mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | ((int(prio_drop) & 3) << 5)
+    work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device)
+    check(lib.xw_tiled_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _p(work), _stream()),
+          'xw_tiled_ode_bwd_multi')
+
+
+def tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True):
+    """u_theta on N paths on the tiled family: (u[L,N], Y[L,H,N] or None)"""
+    d, N = xT.shape
+    L = t.shape[0]
+    u = torch.empty(L, N, dtype=F64, device=xT.device)
+    Y = torch.empty(L, H, N, dtype=F64, device=xT.device) if want_Y else None
+    tiled_ode_fwd_multi([dict(xT=xT, start=start, u=u, Y=Y)], t, theta, method, H, K, m)
+    return u, Y
+
+
+def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):
+    """the reverse sweep on the tiled family: (gx[d,N], gs[N], gslab[nslab,P_u]) -- entries not requested are None"""
+    d, N = xT.shape
+    dev = xT.device
+    gx = torch.empty(d, N, dtype=F64, device=dev) if want_x else None
+    gs = torch.empty(N, dtype=F64, device=dev) if want_x else None
+    gslab = torch.empty(lib.xw_tiled_ode_bwd_slabs(N), theta_size(d, H, K), dtype=F64, device=dev) if want_params else None
+    tiled_ode_bwd_multi([dict(xT=xT, start=start, Y=Y, ubar=ubar, gx=gx, gs=gs, gslab=gslab)], t, theta, method, H, K, m,
+                        want_x, want_params)
+    return gx, gs, gslab
 
 
 def ode_bwd_slabs(N):
@@ -403,6 +519,8 @@ def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_
     """u[L,N] of one group with any served solver: ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
     Hn: the network's u_hidden_dim (dopri5's RMS norms)"""
     if method != DOPRI5:
+        if stepper_family(H, K, m) == 'tiled':
+            return tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
         return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
     u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)
     dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps)

@@ -267,10 +267,18 @@ class XNODE(nn.Module):
 
     def bind(self, device):
         """move to the device and alias the parameters to the kernels' blob, at the width of the smallest stepper
-        instantiation that holds this network (kernels.ode_container; equal widths: plain concatenation)"""
+        instantiation that holds this network (kernels.ode_container; equal widths: plain concatenation) -- or at its own widths on
+        the generic and tiled stepper families (kernels.stepper_family)"""
         self.to(device)
         H, K, d = self.hidden_dim, self.hidden_hidden_dim, self.setup['dim']
-        self.kdims = KN.ode_container(H, K, self.num_layers)
+        self.family = KN.stepper_family(H, K, self.num_layers)
+        if self.family == 'tiled' and self.method == KN.DOPRI5:
+            raise XnwanError("solver 'dopri5' runs on the generic path's field code, up to u_hidden_dim %d / u_hidden_hidden_dim %d / "
+                             "u_layers %d; u_hidden_dim = %d, u_hidden_hidden_dim = %d, u_layers = %d need the tiled stepper family, "
+                             "which runs the fixed-grid solvers %s only" % (KN.GENERIC_ODE_MAX + (KN.GENERIC_ODE_MAX_DEPTH, H, K, self.num_layers,
+                                                                              sorted(KN.METHODS))))
+        # (the tiled family: the network's own widths, the generic layout)
+        self.kdims = KN.stepper_kdims(H, K, self.num_layers)
         slots, total = _u_slots(d, H, K, self.kdims[0], self.kdims[1], self.num_layers > 1)
         assert total == KN.theta_size(d, *self.kdims)
         self.blob = Blob(self, device, slots, total)

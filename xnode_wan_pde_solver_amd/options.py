@@ -46,6 +46,8 @@ class EngineOptions:
     use_runner: bool = True             # XW_RUNNER: one C call per eager group sub-step (xw_substep_*)
     capture_exchange: bool = True       # XW_CAPTURE_EXCHANGE: several GPUs on RCCL -- the exchange inside the sub-step graphs
     xproj_min_d: int = 45               # XW_XPROJ_MIN_D: the test network's input layer once per path from this d on
+    tiled_stepper: str = 'beyond'       # XW_TILED_STEPPER: the tiled stepper family only where the others refuse ('beyond'), or also in
+                                        # place of the generic path ('generic'; kernels.stepper_family)
     hw_queues: int = 4                  # GPU_MAX_HW_QUEUES as the HIP runtime sees it (a warning above 4: the schedule is laid out for 4)
     # ---- engine: semantics / checks ---------------------------------------------------------------------------------------
     verify_structure: bool = True       # XW_VERIFY_STRUCTURE: re-probe the coefficient structure every few samples
@@ -90,6 +92,7 @@ class EngineOptions:
         o.use_runner = _flag('XW_RUNNER', o.use_runner)
         o.capture_exchange = _flag('XW_CAPTURE_EXCHANGE', o.capture_exchange)
         o.xproj_min_d = _int('XW_XPROJ_MIN_D', o.xproj_min_d)
+        o.tiled_stepper = os.environ.get('XW_TILED_STEPPER') or o.tiled_stepper
         try:
             o.hw_queues = _int('GPU_MAX_HW_QUEUES', o.hw_queues)
         except ValueError:

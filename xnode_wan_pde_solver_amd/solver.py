@@ -474,6 +474,8 @@ class NODE_WAN_solver:
             'ode_solver': ("dopri5 (adaptive, step sizes chosen on the device per group; its sub-steps run as eager launches, "
                            "controllers read back every %d attempts)" % self.options.dopri5_chunk if eng.dopri5 else
                            '%s (fixed grid: the sample times)' % self.config['solver']),
+            'stepper': {'mfma': 'fused MFMA container %s' % ((eng.H, eng.K),), 'generic': 'generic vector-ALU path (csrc/xw_generic.hip)',
+                        'tiled': 'tiled MFMA family (csrc/xw_tiled.hip)'}[eng.stepper],
             'ranks': 1 if self.world is None else self.world.size,
             'exchange': None if self.world is None else ('xw_allreduce (RCCL) on the stream: inside the sub-step graphs / the group runner'
                                                          if self.world.capturable else 'torch.distributed, staged through the host'),
