@@ -216,6 +216,23 @@ int xw_disc_bwd_slabs(int N, int L);
 int xw_disc_bwd(const double* xT, const double* t, const double* tpp, const double* phi, const double* vbar,
                 int N, int L, int d, int W, int q, const double* act, double* gslab, void* stream);
 
+/* ---- the TILED test-network family (csrc/xw_disc_tiled.hip): v_phi at its own width, 1 <= W <= 256, 0 <= q <= 32, d + 2 <= 128 ----
+ * phi in the plain layout xw_phi_size(d, W); every layer on v_mfma_f64_16x16x4.  The same arguments, outputs and slab format as
+ * xw_disc_fwd_xproj / xw_disc_bwd, with these differences:
+ *   xw_disc_tiled_ok      : 1 when (d, W, q) is served, else 0
+ *   xw_disc_tiled_act_rows: rows of the record, (q + 1) W (XW_E_DIMS beyond the limits); columns as for xw_disc_act_rows
+ *                           (N L rounded up to a multiple of 16), layout the family's own
+ *   xw_disc_tiled_fwd     : the fused input gradient (gxv, gtv) at any q <= 32; xproj must be NULL (XW_E_ARG)
+ *   xw_disc_tiled_bwd     : from the record only (act == NULL: XW_E_DIMS); gslab[xw_disc_bwd_slabs(N, L)][P_v], every slab written
+ * W > 256, q > 32 or d + 2 > 128: XW_E_DIMS.  No float atomics, no host synchronisation. */
+int xw_disc_tiled_ok(int d, int W, int q);
+int xw_disc_tiled_act_rows(int W, int q);
+int xw_disc_tiled_fwd(const double* xT, const double* t, const double* tpp, const double* phi,
+                      int N, int L, int d, int W, int q, double* v, double* vt, double* gxv, double* gtv, int ngrad,
+                      int max_blocks, double* act, const double* xproj, void* stream);
+int xw_disc_tiled_bwd(const double* xT, const double* t, const double* tpp, const double* phi, const double* vbar,
+                      int N, int L, int d, int W, int q, const double* act, double* gslab, void* stream);
+
 /* ---- weak functional and cotangents (src/loss.py:46-96) -----------------------------------------------------------
  * scal[16] (device, float64): 0 I   1 S=sum v^2   2 SSE_init   3 SSE_bdry   4 loss_u   5 loss_v   6 int
  *                             7 sum u   8 sum d(phi)/dt  (pairwise groups only, folded into I by xw_pair_fold)   (rest reserved)

@@ -96,6 +96,11 @@ SIGNATURES = {
     'xw_disc_gradx': [c_f32p, c_f32p, c_f32p, c_f64p, c_f64p, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_vp],
     'xw_disc_bwd_slabs': [c_int, c_int],
     'xw_disc_bwd': [c_f32p, c_f32p, c_f32p, c_f64p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_vp],
+    'xw_disc_tiled_ok': [c_int, c_int, c_int],
+    'xw_disc_tiled_act_rows': [c_int, c_int],
+    'xw_disc_tiled_fwd': [c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_int,
+                          c_int, c_f64p, c_f64p, c_vp],
+    'xw_disc_tiled_bwd': [c_f32p, c_f32p, c_f32p, c_f64p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_vp],
     'xw_mt19937_uniform_f32': [c_vp, ctypes.c_long, c_vp, ctypes.c_long, ctypes.c_float, ctypes.c_float, c_int],
     'xw_gather_fields': [c_vp, c_int, ctypes.c_long, c_vp],
     'xw_mt19937_legacy_normal_f64': [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), c_vp, ctypes.c_long],

@@ -211,7 +211,13 @@ class Engine:
                                  "u_layers = %d): its field code is the generic path's, up to %s and u_layers %d; the tiled family runs "
                                  "the fixed-grid solvers %s" % (self.H, self.K, self.m, KN.GENERIC_ODE_MAX, KN.GENERIC_ODE_MAX_DEPTH,
                                                                 sorted(KN.METHODS)))
-        self.generic = (self.stepper == 'generic', KN.disc_generic(self.W))
+        # the test network's family (kernels.testnet_family): today's entry points (MFMA containers, generic path) or the tiled
+        # family (csrc/xw_disc_tiled.hip: widths up to 256, depths up to 32, at the network's own width)
+        self.testnet = getattr(v_mod, 'family', None) or KN.testnet_family(config['v_hidden_dim'], self.q)
+        self.testnet_tiled = self.testnet == 'tiled'
+        if self.testnet_tiled and self.W != config['v_hidden_dim']:
+            raise XnwanError('the tiled test-network family reads phi at the network\'s own width; the module was bound at %d' % self.W)
+        self.generic = (self.stepper == 'generic', not self.testnet_tiled and KN.disc_generic(self.W))
         if any(self.generic):
             import warnings
             which = ' and '.join(n_ for n_, g_ in zip(('u_theta (u_hidden_dim %d, u_hidden_hidden_dim %d, u_layers %d)' % (self.H, self.K, self.m),
@@ -222,8 +228,9 @@ class Engine:
         # XW_XPROJ_MIN_D: from which d on.  In the sub-step cycle the split form wins from d ~ 45 on and not below, at 131072 points as at
         # a million (profiles/r05_xproj.txt: headline d = 20 0.488 against 0.473 ms per sub-step -- the small launch is one more dependent
         # node on the critical chain --, d = 20 at 16384 x 64 3.41 against 3.38; d = 50 -1.3 %, BASELINE configs[2] -2.7 %, [3] -6.5 %).
-        self.xproj_min_d = 1 << 30 if self.generic[1] else int(opt.xproj_min_d)
-        if self.W > 64 and not self.generic[1]:
+        # (the tiled family hoists nothing: no table, at any width and depth)
+        self.xproj_min_d = 1 << 30 if (self.generic[1] or self.testnet_tiled) else int(opt.xproj_min_d)
+        if self.W > 64 and not self.generic[1] and not self.testnet_tiled:
             self.xproj_min_d = 0        # (the 128-wide container: 131 KB of Vh fragments leave no LDS for input-layer fragments -- always the table)
         if self.generic[0] and self.adjoint:
             raise XnwanError('adjoint=True (the continuous adjoint) exists for the MFMA stepper instantiations %s only; u_hidden_dim = %d, '
@@ -317,6 +324,9 @@ class Engine:
             # have no narrow tiles.  Graphs and streams stay on.
             self.use_runner = self.keep_activations = False
             self.narrow = '0'
+        if self.testnet_tiled:
+            # the group runner (xw_substep_*) calls the MFMA entry points directly; the test network keeps its record (vact)
+            self.use_runner = False
         # Measured (profiles/r04_shard_sweep.md): forward and the sweep without weight gradients gain on shards up to ~2048
         # paths (0.302 -> 0.272 ms per sub-step at 512 paths, 0.332 -> 0.294 at 1024, 0.375 -> 0.367 at 2048); the narrow sweep
         # WITH weight gradients only ties the two-wave duo sweep (88 against 83 us alone) and is left to XW_NARROW_SET=fxp; at
@@ -829,7 +839,7 @@ class Engine:
         # layer inputs of the test network at every point, stored by its forward in the discriminator sub-step and read
         # back by its backward (524 MB at 131072 points)
         # (only the reference's width and depth have a recomputing reverse kernel: everything else always runs from the record)
-        keep_v = self.keep_activations or not KN.disc_recompute(self.W, self.q)
+        keep_v = self.keep_activations or self.testnet_tiled or not KN.disc_recompute(self.W, self.q)
         G.ns_u = KN.ode_bwd_slabs(N)
         G.ns_b = KN.ode_bwd_slabs(Nb) if Nb else 0
         nw = KN.reduce_work_size()

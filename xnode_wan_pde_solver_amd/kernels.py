@@ -146,6 +146,36 @@ def disc_generic(W):
     return W not in DISC_WIDTHS
 
 
+TILED_DISC_MAX = 256                       # csrc/xw_disc_tiled.hip: the tiled test-network family, at the network's own width,
+TILED_DISC_MAX_DEPTH = 32                  # v_layers up to this
+DISC_MAX_GRAD_DEPTH = 16                   # deepest test network the MFMA entry points run with the fused input gradient
+TESTNET_FAMILIES = ('mfma', 'tiled')
+
+
+def testnet_family(W, q):
+    """which family runs a (v_hidden_dim W, v_layers q) test network: 'mfma' (today's C entry points xw_disc_*: the MFMA containers
+    and, between them, the generic path) for W <= 128 and q <= 16, 'tiled' (csrc/xw_disc_tiled.hip) for the rest up to 256 / 32"""
+    if not (1 <= W <= TILED_DISC_MAX and 0 <= q <= TILED_DISC_MAX_DEPTH):
+        raise XnwanError('v_hidden_dim = %d, v_layers = %d: the test-network kernels serve widths up to %d (MFMA containers %s) / %d '
+                         '(generic path) / %d (tiled), depths up to %d / %d / %d'
+                         % (W, q, DISC_WIDTHS[-1], DISC_WIDTHS, GENERIC_DISC_MAX, TILED_DISC_MAX, DISC_MAX_GRAD_DEPTH,
+                            DISC_MAX_GRAD_DEPTH, TILED_DISC_MAX_DEPTH))
+    return 'mfma' if W <= GENERIC_DISC_MAX and q <= DISC_MAX_GRAD_DEPTH else 'tiled'
+
+
+def testnet_kwidth(W, q):
+    """the width the test network's parameter blob is laid out at: the container ('mfma'), the network's own ('tiled')"""
+    return disc_container(W) if testnet_family(W, q) == 'mfma' else W
+
+
+def _disc_family(W, q, family):
+    if family is None:
+        return testnet_family(W, q)
+    if family not in TESTNET_FAMILIES:
+        raise XnwanError('family = %r: one of %s' % (family, TESTNET_FAMILIES))
+    return family
+
+
 def theta_size(d, H, K):
     return lib.xw_theta_size(d, H, K)
 
@@ -569,8 +599,12 @@ def disc_recompute(W, q):
     return W == 50 and q == DISC_UNROLLED_DEPTH
 
 
-def disc_act_rows(W, q):
+def disc_act_rows(W, q, family=None):
     """rows of the activation record disc_fwd can store for disc_bwd: the inputs of the q tied layers + tanh(a_q)"""
+    if _disc_family(W, q, family) == 'tiled':
+        r = lib.xw_disc_tiled_act_rows(W, q)
+        check(min(r, 0), 'xw_disc_tiled_act_rows')
+        return r
     r = lib.xw_disc_act_rows(W, q)
     check(min(r, 0), 'xw_disc_act_rows')
     return r
@@ -606,11 +640,13 @@ def disc_xproj(xT, phi, W, out=None):
 
 
 def disc_fwd(xT, t, phi, W, q, tpp=None, want_vt=True, v=None, vt=None, gxv=None, gtv=None, ngrad=0, max_blocks=0, act=None,
-             xproj=None):
+             xproj=None, family=None):
     """v_phi and dv/dt.  Path mode: points (t[l], x_n) -> [L,N].  Point mode (tpp[N]): points (tpp[n], x_n) -> [1,N].
     gxv[d,ngrad] / gtv[ngrad]: also return the input gradient of v at the leading ngrad points (time-major order).
     act[disc_act_rows(W, q), disc_act_cols(L*N)]: also store the layer inputs, for disc_bwd(act=...).
-    xproj[disc_xproj_rows(W),N] (path mode, MFMA widths): disc_xproj's table -- the input layer then costs one load per row and point."""
+    xproj[disc_xproj_rows(W),N] (path mode, MFMA widths): disc_xproj's table -- the input layer then costs one load per row and point.
+    family: 'mfma' / 'tiled' in place of testnet_family(W, q)."""
+    family = _disc_family(W, q, family)
     _need_gpu()
     d, N = xT.shape
     L = 1 if tpp is not None else t.shape[0]
@@ -623,7 +659,13 @@ def disc_fwd(xT, t, phi, W, q, tpp=None, want_vt=True, v=None, vt=None, gxv=None
     if gxv is not None:
         _chk(gxv, F64, (d, ngrad), 'gxv'); _chk(gtv, F64, (ngrad,), 'gtv')
     if act is not None:
-        _chk(act, F64, (disc_act_rows(W, q), disc_act_cols(L * N)), 'act')
+        _chk(act, F64, (disc_act_rows(W, q, family), disc_act_cols(L * N)), 'act')
+    if family == 'tiled':
+        if xproj is not None:
+            raise XnwanError('the tiled test-network family takes no x-projection table')
+        check(lib.xw_disc_tiled_fwd(_p(xT), _p(t), _p(tpp), _p(phi), N, L, d, W, q, _p(v), _p(vt if want_vt else None), _p(gxv),
+                                    _p(gtv), int(ngrad), int(max_blocks), _p(act), None, _stream()), 'xw_disc_tiled_fwd')
+        return v, (vt if want_vt else None)
     if xproj is not None:
         _chk(xproj, F64, (disc_xproj_rows(W), N), 'xproj')
     check(lib.xw_disc_fwd_xproj(_p(xT), _p(t), _p(tpp), _p(phi), N, L, d, W, q, _p(v), _p(vt if want_vt else None), _p(gxv),
@@ -631,8 +673,9 @@ def disc_fwd(xT, t, phi, W, q, tpp=None, want_vt=True, v=None, vt=None, gxv=None
     return v, (vt if want_vt else None)
 
 
-def disc_gradx(xT, t, phi, W, q, tpp=None, vbar=None, gxv=None, gtv=None):
+def disc_gradx(xT, t, phi, W, q, tpp=None, vbar=None, gxv=None, gtv=None, family=None):
     """input gradient of <vbar, v>: (nabla_x)[d,N] and (d/dt)[N] at the points (tpp[n] or t[0], x_n); vbar None = ones."""
+    family = _disc_family(W, q, family)
     _need_gpu()
     d, N = xT.shape
     _chk(xT, F64, (d, N), 'xT'); _chk(phi, F64, (phi_size(d, W),), 'phi'); _chk(t, F64, None, 't'); _chk(tpp, F64, (N,), 'tpp')
@@ -642,10 +685,11 @@ def disc_gradx(xT, t, phi, W, q, tpp=None, vbar=None, gxv=None, gtv=None):
     if vbar is not None:
         vbar = vbar.reshape(-1)
         _chk(vbar, F64, (N,), 'vbar')
-    if not disc_recompute(W, q):
-        # other depths / widths: the forward kernel's fused input gradient (any q <= 16), scaled by the cotangent
+    if family == 'tiled' or not disc_recompute(W, q):
+        # other depths / widths: the forward kernel's fused input gradient (any q <= 16; the tiled family: q <= 32), scaled by
+        # the cotangent
         t0 = t[:1] if tpp is None else None
-        disc_fwd(xT, t0, phi, W, q, tpp=tpp, want_vt=False, gxv=gxv, gtv=gtv, ngrad=N)
+        disc_fwd(xT, t0, phi, W, q, tpp=tpp, want_vt=False, gxv=gxv, gtv=gtv, ngrad=N, family=family)
         if vbar is not None:
             gxv.mul_(vbar)
             gtv.mul_(vbar)
@@ -658,9 +702,10 @@ def disc_bwd_slabs(N, L):
     return lib.xw_disc_bwd_slabs(N, L)
 
 
-def disc_bwd(xT, t, phi, vbar, W, q, tpp=None, gslab=None, act=None):
+def disc_bwd(xT, t, phi, vbar, W, q, tpp=None, gslab=None, act=None, family=None):
     """parameter gradient of <vbar, v> as partial slabs [nslab, P_v].  act: the record disc_fwd stored for the same phi and
     points (skips the forward recompute)."""
+    family = _disc_family(W, q, family)
     _need_gpu()
     d, N = xT.shape
     L = 1 if tpp is not None else t.shape[0]
@@ -670,12 +715,16 @@ def disc_bwd(xT, t, phi, vbar, W, q, tpp=None, gslab=None, act=None):
     ns = disc_bwd_slabs(N, L)
     gslab = torch.empty(ns, P, dtype=F64, device=xT.device) if gslab is None else gslab
     _chk(gslab, F64, (ns, P), 'gslab')
-    if act is None and not disc_recompute(W, q):
+    if act is None and (family == 'tiled' or not disc_recompute(W, q)):
         # the recomputing kernel exists at the reference's width and depth only: store the record first, then reverse from it
-        act = torch.empty(disc_act_rows(W, q), disc_act_cols(L * N), dtype=F64, device=xT.device)
-        disc_fwd(xT, t, phi, W, q, tpp=tpp, want_vt=False, act=act)
+        act = torch.empty(disc_act_rows(W, q, family), disc_act_cols(L * N), dtype=F64, device=xT.device)
+        disc_fwd(xT, t, phi, W, q, tpp=tpp, want_vt=False, act=act, family=family)
     if act is not None:
-        _chk(act, F64, (disc_act_rows(W, q), disc_act_cols(L * N)), 'act')
+        _chk(act, F64, (disc_act_rows(W, q, family), disc_act_cols(L * N)), 'act')
+    if family == 'tiled':
+        check(lib.xw_disc_tiled_bwd(_p(xT), _p(t), _p(tpp), _p(phi), _p(vbar), N, L, d, W, q, _p(act), _p(gslab), _stream()),
+              'xw_disc_tiled_bwd')
+        return gslab
     check(lib.xw_disc_bwd(_p(xT), _p(t), _p(tpp), _p(phi), _p(vbar), N, L, d, W, q, _p(act), _p(gslab), _stream()),
           'xw_disc_bwd')
     return gslab

@@ -361,7 +361,10 @@ class TestNet(nn.Module):
     def bind(self, device):
         self.to(device)
         d = self.input.in_features - 1
-        self.kwidth = KN.disc_container(self.hidden_dim)
+        # the family (kernels.testnet_family): the MFMA containers / generic path at the container's width, or the tiled
+        # family at the network's own width
+        self.family = KN.testnet_family(self.hidden_dim, self.num_layers)
+        self.kwidth = KN.testnet_kwidth(self.hidden_dim, self.num_layers)
         slots, total = _v_slots(d, self.hidden_dim, self.kwidth)
         assert total == KN.phi_size(d, self.kwidth)
         self.blob = Blob(self, device, slots, total)
