@@ -136,6 +136,22 @@ int xw_tiled_ode_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, 
 int xw_tiled_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
                            int method, int L, int d, int H, int K, int m, int mode, double* work, void* stream);
 
+/* ---- solver 'explicit_adams' on the tiled family: torchdiffeq's fixed-grid Adams-Bashforth (fixed_adams.py, implicit=False) ---
+ * On the requested grid: f_n = F(t_n, y_n) joins a history of at most 11 field values; steps 0 and 1 are rk4 steps (3/8 rule,
+ * method 2) with k1 = f_n, step n >= 2 is y_{n+1} = y_n + sum_{j < ord} dt_n beta[ord][j] f_{n-j}, ord = min(n + 1, 11) (AB3 ..
+ * AB11, fixed coefficients at the current dt).  Widths, jobs, outputs, mode bits and slab format as xw_tiled_ode_fwd_multi /
+ * xw_tiled_ode_bwd_multi (no method argument); the workspace per 16-path tile is xw_adams_tiled_work(...) doubles (the history
+ * ring comes on top of the tiled family's own).  The sweep reverses the recurrence from the checkpoints Y, step sizes as constants.
+ *   xw_adams_coef: the k-step Adams-Bashforth row (k = 1..11, most recent value first) into out[0..k) on the host -- the
+ *                  coefficients the kernels use
+ * xw_tiled_ode_fwd_multi / _bwd_multi, xw_ode_*_multi and the generic path refuse its id (kernels.ADAMS = 4): XW_E_ARG. */
+int xw_adams_coef(int k, double* out);
+int xw_adams_tiled_work(int sweep, int d, int H, int K, int m);
+int xw_adams_tiled_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, const double* theta,
+                             int L, int d, int H, int K, int m, double* zero16, double* work, void* stream);
+int xw_adams_tiled_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
+                             int L, int d, int H, int K, int m, int mode, double* work, void* stream);
+
 /* ---- solver 'dopri5': torchdiffeq's adaptive Dormand-Prince 5(4) (the default method of odeint, src/model.py:103-106) -----
  * One step size per JOB (= one odeint call of the reference: a group of paths), chosen on the device: every attempt is one
  * launch for all jobs, the last block of a job to finish it reduces the scaled error (RMS over N x Hn entries, Hn = the network's

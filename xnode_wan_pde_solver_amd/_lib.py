@@ -78,6 +78,12 @@ SIGNATURES = {
                                c_f64p, c_vp],
     'xw_tiled_ode_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                c_f64p, c_vp],
+    'xw_adams_coef': [c_int, c_vp],
+    'xw_adams_tiled_work': [c_int, c_int, c_int, c_int, c_int],
+    'xw_adams_tiled_fwd_multi': [ctypes.POINTER(XwOdeFwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p,
+                                 c_vp],
+    'xw_adams_tiled_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p,
+                                 c_vp],
     'xw_dopri5_ctl_size': [],
     'xw_dopri5_work_size': [c_int],
     'xw_dopri5_init': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl,

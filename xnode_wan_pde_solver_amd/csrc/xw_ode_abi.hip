@@ -42,6 +42,7 @@ extern "C" int xw_ode_act_rows(int method, int H, int K, int m) {
 
 extern "C" int xw_ode_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, const double* theta, int method, int L,
                                 int d, int H, int K, int m, double* zero16, void* stream) {
+  if (method < 0 || method > 2) return XW_E_ARG;    // fixed-grid ids 0..2 only (dopri5, explicit_adams: entry points of their own)
 #define CALL(HH, KK) if (H == HH && K == KK && m <= XW_ODE_MAX_LAYERS) return xw_ode_fwd_multi_w##HH##_##KK(jobs, njobs, t, theta, method, L, d, m, zero16, stream);
   XW_ODE_WIDTHS(CALL)
 #undef CALL
@@ -57,6 +58,7 @@ extern "C" int xw_ode_fwd(const double* xT, const double* t, const double* start
 
 extern "C" int xw_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta, int method, int L,
                                 int d, int H, int K, int m, int mode, void* stream) {
+  if (method < 0 || method > 2) return XW_E_ARG;
 #define CALL(HH, KK) if (H == HH && K == KK && m <= XW_ODE_MAX_LAYERS) return xw_ode_bwd_multi_w##HH##_##KK(jobs, njobs, t, theta, method, L, d, m, mode, stream);
   XW_ODE_WIDTHS(CALL)
 #undef CALL

@@ -196,8 +196,12 @@ class Engine:
         # orders of magnitude slower -- said once, loudly
         # the stepper family (kernels.stepper_family): the fused MFMA containers, the generic path or the tiled family
         # (csrc/xw_tiled.hip: any width up to 256 at the network's own widths, fixed grid; EngineOptions.tiled_stepper)
-        self.stepper = KN.stepper_family(config['u_hidden_dim'], config['u_hidden_hidden_dim'], self.m, opt.tiled_stepper)
+        # (solver 'explicit_adams': the tiled family at every width -- its only family)
+        self.stepper = KN.stepper_family(config['u_hidden_dim'], config['u_hidden_hidden_dim'], self.m, opt.tiled_stepper, self.method)
         self.tiled = self.stepper == 'tiled'
+        if self.method == KN.ADAMS and self.adjoint:
+            from .nets import ADAMS_ADJOINT_REFUSED
+            raise XnwanError(ADAMS_ADJOINT_REFUSED)
         if self.tiled:
             if (self.H, self.K) != (config['u_hidden_dim'], config['u_hidden_hidden_dim']):
                 raise XnwanError('the tiled stepper family reads theta at the network\'s own widths; the module was bound at %s'

@@ -9,7 +9,8 @@ from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, 
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 DOPRI5 = 3                                 # solver 'dopri5' (adaptive, dopri5_fwd / dopri5_sweep below): not a fixed-grid method id
-ADAPTIVE_REFUSED = ('dopri8', 'bosh3', 'fehlberg2', 'adaptive_heun', 'adams', 'explicit_adams', 'implicit_adams',
+ADAMS = 4                                  # solver 'explicit_adams' (fixed-grid Adams-Bashforth): the tiled family only (adams_tiled_* below)
+ADAPTIVE_REFUSED = ('dopri8', 'bosh3', 'fehlberg2', 'adaptive_heun', 'adams', 'implicit_adams',
                     'fixed_adams', 'scipy_solver')   # torchdiffeq's other methods: not served
 F32, F64 = torch.float32, torch.float64
 
@@ -59,9 +60,11 @@ def _stream():
 def method_id(name):
     if name == 'dopri5':
         return DOPRI5
+    if name == 'explicit_adams':
+        return ADAMS
     if name not in METHODS:
-        raise XnwanError("solver %r is not served: the fixed-grid schemes %s and the adaptive 'dopri5' are (no other adaptive "
-                         "torchdiffeq method)" % (name, sorted(METHODS)))
+        raise XnwanError("solver %r is not served: the fixed-grid schemes %s, the fixed-grid Adams-Bashforth 'explicit_adams' and the "
+                         "adaptive 'dopri5' are (no other adaptive torchdiffeq method, no predictor-corrector Adams)" % (name, sorted(METHODS)))
     return METHODS[name]
 
 
@@ -108,16 +111,19 @@ TILED_ODE_MAX_DEPTH = 32                   # this, fixed-grid methods only
 TILED_POLICIES = ('beyond', 'generic')     # EngineOptions.tiled_stepper
 
 
-def stepper_family(H, K, m=1, policy='beyond'):
+def stepper_family(H, K, m=1, policy='beyond', method=None):
     """which stepper family runs a (u_hidden_dim H, u_hidden_hidden_dim K, u_layers m) field: 'mfma' (the fused containers),
     'generic' (csrc/xw_generic.hip) or 'tiled' (csrc/xw_tiled.hip).  policy 'beyond': the tiled family only where the other two
-    refuse; 'generic': also in place of the generic path."""
+    refuse; 'generic': also in place of the generic path.  method == ADAMS (explicit_adams): the tiled family at every width it
+    serves -- the only family with that solver."""
     if policy not in TILED_POLICIES:
         raise XnwanError('tiled_stepper = %r: one of %s' % (policy, TILED_POLICIES))
     if not (1 <= H <= TILED_ODE_MAX[0] and 1 <= K <= TILED_ODE_MAX[1] and 1 <= m <= TILED_ODE_MAX_DEPTH):
         raise XnwanError('u_hidden_dim = %d, u_hidden_hidden_dim = %d, u_layers = %d: the stepper kernels serve widths up to %s (MFMA) / '
                          '%s (generic path) / %s (tiled), depths up to %d / %d / %d'
                          % (H, K, m, ODE_WIDTHS[-1], GENERIC_ODE_MAX, TILED_ODE_MAX, ODE_MAX_DEPTH, GENERIC_ODE_MAX_DEPTH, TILED_ODE_MAX_DEPTH))
+    if method == ADAMS:
+        return 'tiled'
     try:
         Hc, Kc = ode_container(H, K, m)
     except XnwanError:
@@ -127,9 +133,9 @@ def stepper_family(H, K, m=1, policy='beyond'):
     return 'tiled' if policy == 'generic' else 'generic'
 
 
-def stepper_kdims(H, K, m=1, policy='beyond'):
+def stepper_kdims(H, K, m=1, policy='beyond', method=None):
     """the widths the parameter blob is laid out at: the MFMA container, or the network's own (generic, tiled)"""
-    return ode_container(H, K, m) if stepper_family(H, K, m, policy) != 'tiled' else (H, K)
+    return ode_container(H, K, m) if stepper_family(H, K, m, policy, method) != 'tiled' else (H, K)
 
 
 def disc_container(W):
@@ -297,22 +303,35 @@ def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_on
     check(lib.xw_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _stream()), 'xw_ode_bwd_multi')
 
 
-def tiled_ode_work(sweep, d, H, K, m, tiles, dev):
-    """the workspace of one tiled launch over `tiles` 16-path tiles (csrc/xw_tiled.hip: per-tile vectors)"""
-    per = lib.xw_tiled_ode_work(1 if sweep else 0, d, H, K, m)
+def tiled_ode_work(sweep, d, H, K, m, tiles, dev, method=None):
+    """the workspace of one tiled launch over `tiles` 16-path tiles (csrc/xw_tiled.hip: per-tile vectors; explicit_adams: and
+    its history)"""
+    per = (lib.xw_adams_tiled_work if method == ADAMS else lib.xw_tiled_ode_work)(1 if sweep else 0, d, H, K, m)
     check(min(per, 0), 'xw_tiled_ode_work')
     return torch.empty(per * tiles, dtype=F64, device=dev)
 
 
 def tiled_ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, prio_drop=0, **_hints):
     """ode_fwd_multi on the tiled family (csrc/xw_tiled.hip): jobs as there (act, act_x_only and narrow are hints the family
-    does not take: no activation store, no narrow tiles); theta at the network's own widths"""
+    does not take: no activation store, no narrow tiles); theta at the network's own widths.  method ADAMS: adams_tiled_fwd_multi"""
+    if method == ADAMS:
+        return adams_tiled_fwd_multi(jobs, t, theta, H, K, m, zero16=zero16, prio_drop=prio_drop)
+    _tiled_fwd(jobs, t, theta, method, H, K, m, zero16, prio_drop)
+
+
+def adams_tiled_fwd_multi(jobs, t, theta, H, K, m, zero16=None, prio_drop=0, **_hints):
+    """solver 'explicit_adams' forward on the tiled family (xw_adams_tiled_fwd_multi): jobs, outputs and widths as
+    tiled_ode_fwd_multi"""
+    _tiled_fwd(jobs, t, theta, ADAMS, H, K, m, zero16, prio_drop)
+
+
+def _tiled_fwd(jobs, t, theta, method, H, K, m, zero16, prio_drop):
     _need_gpu()
     L = t.shape[0]
     d = jobs[0]['xT'].shape[0]
     _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
-    if method not in METHODS.values():
-        raise XnwanError('the tiled stepper family runs the fixed-grid methods %s only' % sorted(METHODS))
+    if method != ADAMS and method not in METHODS.values():
+        raise XnwanError("the tiled stepper family runs the fixed-grid methods %s and 'explicit_adams' only" % sorted(METHODS))
     arr = (XwOdeFwdJob * len(jobs))()
     for a, j in zip(arr, jobs):
         N = j['xT'].shape[1]
@@ -321,15 +340,35 @@ def tiled_ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, prio_drop=
         a.xT, a.start, a.u, a.Y, a.act, a.N = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y')), 0, N
         a.act_x_only, a.narrow, a.prio_drop = 0, 0, int(prio_drop)
     _chk(zero16, F64, (16,), 'zero16')
-    work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device)
-    check(lib.xw_tiled_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _p(work), _stream()),
-          'xw_tiled_ode_fwd_multi')
+    work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device, method)
+    if method == ADAMS:
+        check(lib.xw_adams_tiled_fwd_multi(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, _p(zero16), _p(work), _stream()),
+              'xw_adams_tiled_fwd_multi')
+    else:
+        check(lib.xw_tiled_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _p(work), _stream()),
+              'xw_tiled_ode_fwd_multi')
 
 
 def tiled_ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False,
                         prio_drop=0):
     """ode_bwd_multi on the tiled family: the same jobs (stored cotangent or residual form), outputs and slab format; the sweep
-    recomputes from the checkpoints Y.  No continuous adjoint, no narrow tiles."""
+    recomputes from the checkpoints Y.  No continuous adjoint, no narrow tiles.  method ADAMS: adams_tiled_bwd_multi"""
+    if method == ADAMS:
+        return adams_tiled_bwd_multi(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint,
+                                     narrow=narrow, prio_drop=prio_drop)
+    _tiled_bwd(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop)
+
+
+def adams_tiled_bwd_multi(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False, prio_drop=0):
+    """solver 'explicit_adams' sweep on the tiled family (xw_adams_tiled_bwd_multi): jobs, cotangent forms, outputs and slab
+    format as tiled_ode_bwd_multi; step sizes are constants of the reverse pass"""
+    if adjoint:
+        raise XnwanError("solver 'explicit_adams' with adjoint=True (the continuous adjoint) is not served: its sweep reverses the "
+                         "Adams-Bashforth recurrence (u_hidden_dim = %d, u_hidden_hidden_dim = %d)" % (H, K))
+    _tiled_bwd(jobs, t, theta, ADAMS, H, K, m, want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop)
+
+
+def _tiled_bwd(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop):
     _need_gpu()
     if adjoint:
         raise XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
@@ -357,9 +396,13 @@ def tiled_ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_
         a.gx, a.gs, a.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
         _set_res(a, j, L, N)
     mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | ((int(prio_drop) & 3) << 5)
-    work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device)
-    check(lib.xw_tiled_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _p(work), _stream()),
-          'xw_tiled_ode_bwd_multi')
+    work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device, method)
+    if method == ADAMS:
+        check(lib.xw_adams_tiled_bwd_multi(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _p(work), _stream()),
+              'xw_adams_tiled_bwd_multi')
+    else:
+        check(lib.xw_tiled_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _p(work), _stream()),
+              'xw_tiled_ode_bwd_multi')
 
 
 def tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True):
@@ -549,7 +592,7 @@ def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_
     """u[L,N] of one group with any served solver: ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
     Hn: the network's u_hidden_dim (dopri5's RMS norms)"""
     if method != DOPRI5:
-        if stepper_family(H, K, m) == 'tiled':
+        if stepper_family(H, K, m, method=method) == 'tiled':
             return tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
         return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
     u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)

@@ -240,6 +240,11 @@ class HiddenField(nn.Module):
         raise XnwanError('the field is only evaluated inside the fused HIP stepper (XNODE.forward)')
 
 
+ADAMS_ADJOINT_REFUSED = ("solver 'explicit_adams' with adjoint=True is not served: explicit_adams runs on the tiled stepper family "
+                         "only, whose sweep reverses the steps taken (the discrete adjoint, step sizes as constants); torchdiffeq's "
+                         "continuous adjoint exists for the fixed-grid schemes on the MFMA containers")
+
+
 class XNODE(nn.Module):
     """u_theta.  forward(inputs[N, L, d+1]) -> [N, L, 1] for a group of equal-length paths (time in channel 0)."""
 
@@ -255,6 +260,8 @@ class XNODE(nn.Module):
         if self.method == KN.DOPRI5 and adjoint:
             raise XnwanError("solver 'dopri5' with adjoint=True is not served: the sweep reverses the accepted steps (the "
                              "discrete adjoint, step sizes as constants); torchdiffeq's continuous adjoint of an adaptive solve is not built")
+        if self.method == KN.ADAMS and adjoint:
+            raise XnwanError(ADAMS_ADJOINT_REFUSED)
         self.rtol, self.atol = KN.DOPRI5_RTOL, KN.DOPRI5_ATOL        # (dopri5: torchdiffeq's defaults, as the reference gets them)
         self.dopri5_chunk, self.dopri5_max_steps = KN.DOPRI5_CHUNK, KN.DOPRI5_MAX_STEPS
         self._ode_fn = _Dopri5Fn if self.method == KN.DOPRI5 else _OdeFn
@@ -271,14 +278,14 @@ class XNODE(nn.Module):
         the generic and tiled stepper families (kernels.stepper_family)"""
         self.to(device)
         H, K, d = self.hidden_dim, self.hidden_hidden_dim, self.setup['dim']
-        self.family = KN.stepper_family(H, K, self.num_layers)
+        self.family = KN.stepper_family(H, K, self.num_layers, method=self.method)
         if self.family == 'tiled' and self.method == KN.DOPRI5:
             raise XnwanError("solver 'dopri5' runs on the generic path's field code, up to u_hidden_dim %d / u_hidden_hidden_dim %d / "
                              "u_layers %d; u_hidden_dim = %d, u_hidden_hidden_dim = %d, u_layers = %d need the tiled stepper family, "
                              "which runs the fixed-grid solvers %s only" % (KN.GENERIC_ODE_MAX + (KN.GENERIC_ODE_MAX_DEPTH, H, K, self.num_layers,
                                                                               sorted(KN.METHODS))))
         # (the tiled family: the network's own widths, the generic layout)
-        self.kdims = KN.stepper_kdims(H, K, self.num_layers)
+        self.kdims = KN.stepper_kdims(H, K, self.num_layers, method=self.method)
         slots, total = _u_slots(d, H, K, self.kdims[0], self.kdims[1], self.num_layers > 1)
         assert total == KN.theta_size(d, *self.kdims)
         self.blob = Blob(self, device, slots, total)

@@ -28,7 +28,7 @@ def xnode_forward(X: torch.Tensor, start: torch.Tensor, blob: torch.Tensor, meth
     xT = X[:, 0, 1:].detach().to(F64).t().contiguous()
     t = X[0, :, 0].detach().to(F64).contiguous()
     s = start.detach().to(F64).reshape(-1).contiguous()
-    if KN.stepper_family(H, K, m) == 'tiled':          # (H, K: the blob's widths -- the network's own on this family)
+    if KN.stepper_family(H, K, m, method=method) == 'tiled':    # (H, K: the blob's widths -- the network's own on this family)
         u, Y = KN.tiled_ode_fwd(xT, t, s, blob, method, H, K, m, want_Y=keep)
     else:
         u, Y = KN.ode_fwd(xT, t, s, blob, method, H, K, m, want_Y=keep)
@@ -49,7 +49,7 @@ def xnode_backward(gu: torch.Tensor, X: torch.Tensor, start: torch.Tensor, Y: to
     t = X[0, :, 0].detach().to(F64).contiguous()
     s = start.detach().to(F64).reshape(-1).contiguous()
     ubar = gu.squeeze(2).t().contiguous().to(F64)
-    if KN.stepper_family(H, K, m) == 'tiled':
+    if KN.stepper_family(H, K, m, method=method) == 'tiled':
         if adjoint:
             raise KN.XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
                                 'u_hidden_hidden_dim = %d, u_layers = %d)' % (H, K, m))

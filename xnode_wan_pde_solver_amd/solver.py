@@ -473,7 +473,8 @@ class NODE_WAN_solver:
                                                                                  eng.structure.c_kappa is not None else 'launch by launch'),
             'ode_solver': ("dopri5 (adaptive, step sizes chosen on the device per group; its sub-steps run as eager launches, "
                            "controllers read back every %d attempts)" % self.options.dopri5_chunk if eng.dopri5 else
-                           '%s (fixed grid: the sample times)' % self.config['solver']),
+                           '%s (fixed grid: the sample times%s)' % (self.config['solver'], ', Adams-Bashforth AB3 .. AB11 after two rk4 '
+                                                                     'start-up steps' if self.config['solver'] == 'explicit_adams' else '')),
             'stepper': {'mfma': 'fused MFMA container %s' % ((eng.H, eng.K),), 'generic': 'generic vector-ALU path (csrc/xw_generic.hip)',
                         'tiled': 'tiled MFMA family (csrc/xw_tiled.hip)'}[eng.stepper],
             'testnet': ('tiled MFMA family at width %d (csrc/xw_disc_tiled.hip)' % eng.W if eng.testnet == 'tiled' else
