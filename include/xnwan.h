@@ -190,6 +190,22 @@ typedef struct { XwOdeBwdJob b; const double* rec_y; const double* rec_t; const 
 int xw_dopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K,
                     int m, int mode, void* stream);
 
+/* ---- solver 'dopri5' on the tiled stepper family (csrc/xw_tdopri.hip): the same algorithm, controller, record and status codes
+ * with the field on v_mfma_f64_16x16x4, one wave per tile of 16 paths, at H, K <= 256 and m <= 32 (xw_tiled_ode_ok).  The job
+ * structs are those above, with job.work[xw_tdopri5_part_size(N)] (one partial per TILE); a record written by either forward can be
+ * swept by either sweep at widths both serve.  work: xw_tdopri5_work(sweep, d, H, K, m) doubles per tile (a multiple of 16) times
+ * the launch's tiles, sum over the jobs of (N + 15) / 16 in job order; per launch, nothing in it outlives the call's kernels.
+ * XW_E_DIMS beyond those widths and for mode bits 3 and 4; XW_E_ARG for L < 1, njobs outside 1..8, a sweep without a requested
+ * output or with mode bit 2 without bits 0 and 1 -- all before any job is read or anything is launched. */
+int xw_tdopri5_work(int sweep, int d, int H, int K, int m);
+int xw_tdopri5_part_size(int N);
+int xw_tdopri5_init(const XwDopriJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K, int m,
+                    int Hn, double rtol, double atol, double* work, void* stream);
+int xw_tdopri5_attempts(const XwDopriJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K,
+                        int m, int Hn, double rtol, double atol, int max_steps, int n, double* work, void* stream);
+int xw_tdopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const double* t, const double* theta, int L, int d, int H, int K,
+                     int m, int mode, double* work, void* stream);
+
 /* ---- v_phi: discriminator.forward (src/model.py:37-47) + d/dt by forward-mode ------------------------------------
  * Path mode (tpp == NULL): point (l,n) = (t[l], x_n).  Point mode (tpp != NULL): L must be 1, point n = (tpp[n], x_n).
  * v[L,N] out; vt[L,N] out = dv/dt (may be NULL).

@@ -91,6 +91,14 @@ SIGNATURES = {
     'xw_dopri5_attempts': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl,
                            c_dbl, c_int, c_int, c_vp],
     'xw_dopri5_sweep': [ctypes.POINTER(XwDopriSweepJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
+    'xw_tdopri5_work': [c_int, c_int, c_int, c_int, c_int],
+    'xw_tdopri5_part_size': [c_int],
+    'xw_tdopri5_init': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl,
+                        c_f64p, c_vp],
+    'xw_tdopri5_attempts': [ctypes.POINTER(XwDopriJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl,
+                            c_dbl, c_int, c_int, c_f64p, c_vp],
+    'xw_tdopri5_sweep': [ctypes.POINTER(XwDopriSweepJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p,
+                         c_vp],
     'xw_ode_bwd': [c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                    c_f64p, c_f64p, c_f64p, c_vp],
     'xw_disc_fwd': [c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_int,

@@ -1,0 +1,97 @@
+// xw_dopri_ctl.h -- what the two implementations of solver 'dopri5' share (xw_dopri.hip: the field per path on the vector ALU;
+// xw_tdopri.hip: the field per 16-path tile on the matrix pipe): the controller slots, the Dormand-Prince tableau, the dense
+// output, the job pack of a launch and the per-job ticket reduction.  Library-internal; included INSIDE an anonymous namespace,
+// after a gsum64(double) (the sum over the wave) has been declared.
+#pragma once
+
+// controller slots (include/xnwan.h)
+enum { C_T0 = 0, C_DT = 1, C_NACC = 2, C_NATT = 3, C_DONE = 4, C_STATUS = 5, C_H0 = 6, C_D1 = 7, C_RATIO = 8, C_GAP = 9, C_TICKET = 15 };
+
+// Dormand-Prince 5(4) (torchdiffeq _DORMAND_PRINCE_SHAMPINE_TABLEAU, DPS_C_MID): nodes, stage rows (row s feeds stage s from
+// k_0 .. k_{s-1}; row 6 is the 5th-order solution, FSAL), error weights b - b^, and the weights of the midpoint of the dense output
+__constant__ double DP_C[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
+__constant__ double DP_A[7][6] = {
+    {0, 0, 0, 0, 0, 0},
+    {1.0 / 5, 0, 0, 0, 0, 0},
+    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
+    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
+    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
+    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
+    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84}};
+__constant__ double DP_B[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
+__constant__ double DP_E[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
+                               -2187.0 / 6784 + 12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60};
+__constant__ double DP_MID[7] = {6025192743.0 / 30085553152 / 2, 0, 51252292925.0 / 65400821598 / 2,
+                                 -2691868925.0 / 45128329728 / 2, 187940372067.0 / 1594534317056 / 2,
+                                 -1776094331.0 / 19743644256 / 2, 11237099.0 / 235043384 / 2};
+constexpr double DP_SAFETY = 0.9, DP_IFACTOR = 10.0, DP_DFACTOR = 0.2;
+
+// The dense output is the quartic through y0, y1 (x = 1), y_mid (x = 1/2) with slopes dt f0, dt f1 (torchdiffeq _interp_fit):
+// with y1 and y_mid linear in the stages it is p(x) = y0 + dt sum_j w_j(x) k_j, w_j(x) below (w_j(1) = b_j)
+__device__ __forceinline__ void dense_weights(double x, double (&w)[7]) {
+  const double x2 = x * x, x3 = x2 * x, x4 = x3 * x;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {
+    const double b = DP_B[j], cm = DP_MID[j];
+    const double d0 = j == 0 ? 1.0 : 0.0, d6 = j == 6 ? 1.0 : 0.0;
+    w[j] = x * d0 + x2 * (d6 - 4 * d0 - 5 * b + 16 * cm) + x3 * (5 * d0 - 3 * d6 + 14 * b - 32 * cm) +
+           x4 * (2 * d6 - 2 * d0 - 8 * b + 16 * cm);
+  }
+}
+
+#define XW_DOPRI_MAXJOBS 8
+template <class J> struct Jobs {
+  J j[XW_DOPRI_MAXJOBS];
+  int blk0[XW_DOPRI_MAXJOBS + 1];    // first block of every job, prefix sums of (N + 63) / 64
+  int njobs;
+};
+template <class J> __device__ __forceinline__ int job_of(const Jobs<J>& J_, int& lb) {
+  int jb = 0;
+  while (jb + 1 < J_.njobs && (int)blockIdx.x >= J_.blk0[jb + 1]) ++jb;
+  lb = (int)blockIdx.x - J_.blk0[jb];
+  return jb;
+}
+
+// The job's NV partial sums of this block into work[NV lb + i], then its ticket; true in the LAST block of the job to arrive, whose
+// lane 0 then holds the totals (summed in block order: the same bits whatever the arrival order).  Release / acquire as grid_sum.
+template <int NV>
+__device__ __forceinline__ bool job_sum(double (&val)[NV], double* __restrict__ work, double* ctl, int nb, int lb) {
+  __shared__ int is_last;
+  double s[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s[i] = gsum64(val[i]);
+  if (threadIdx.x == 0)
+    for (int i = 0; i < NV; ++i) work[NV * lb + i] = s[i];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(ctl + C_TICKET);
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = t == (unsigned int)nb - 1;
+    if (is_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!is_last) return false;
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < NV; ++i) {
+      double tot = 0.0;
+      for (int b = 0; b < nb; ++b) tot += work[NV * b + i];
+      val[i] = tot;
+    }
+    *ticket = 0u;                                           // (every block of the job has taken its ticket)
+  }
+  return true;
+}
+
+template <class J> int pack_jobs(const J* jobs, int njobs, Jobs<J>& P) {
+  if (!jobs || njobs < 1 || njobs > XW_DOPRI_MAXJOBS) return XW_E_ARG;
+  P.njobs = njobs;
+  P.blk0[0] = 0;
+  for (int i = 0; i < njobs; ++i) P.j[i] = jobs[i];
+  return 0;                                                 // (blk0: by the caller, from the job kind's N)
+}

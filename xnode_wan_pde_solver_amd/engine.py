@@ -170,6 +170,7 @@ class Engine:
         # no segment that holds one can be captured -- decided here, up front: eager launches on one stream, no fused runner
         # (xw_substep_* is fixed-grid), no activation store (the sweeps recompute from the step record)
         self.dopri5 = self.method == KN.DOPRI5
+        self.dopri5_stepper = KN.dopri5_stepper(opt.dopri5_stepper)     # 'vector' | 'tiled': which kernels run its field
         self._dopri_recs = {}
         if self.dopri5 and world is not None:
             raise XnwanError("solver 'dopri5' runs on one GPU: its step sizes are per group and chosen on the device, and a "
@@ -210,11 +211,12 @@ class Engine:
                 raise XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
                                  'u_hidden_hidden_dim = %d, u_layers = %d: it reverses the steps taken; the continuous adjoint exists '
                                  'for the MFMA containers %s, u_layers <= %d)' % (self.H, self.K, self.m, KN.ODE_WIDTHS, KN.ODE_MAX_DEPTH))
-            if self.dopri5:
+            if self.dopri5 and self.dopri5_stepper != 'tiled':
                 raise XnwanError("solver 'dopri5' is not served by the tiled stepper family (u_hidden_dim = %d, u_hidden_hidden_dim = %d, "
                                  "u_layers = %d): its field code is the generic path's, up to %s and u_layers %d; the tiled family runs "
-                                 "the fixed-grid solvers %s" % (self.H, self.K, self.m, KN.GENERIC_ODE_MAX, KN.GENERIC_ODE_MAX_DEPTH,
-                                                                sorted(KN.METHODS)))
+                                 "the fixed-grid solvers %s -- unless EngineOptions.dopri5_stepper = 'tiled' (XW_DOPRI5_STEPPER) selects "
+                                 "dopri5's implementation on that family" % (self.H, self.K, self.m, KN.GENERIC_ODE_MAX,
+                                                                              KN.GENERIC_ODE_MAX_DEPTH, sorted(KN.METHODS)))
         # the test network's family (kernels.testnet_family): today's entry points (MFMA containers, generic path) or the tiled
         # family (csrc/xw_disc_tiled.hip: widths up to 256, depths up to 32, at the network's own width)
         self.testnet = getattr(v_mod, 'family', None) or KN.testnet_family(config['v_hidden_dim'], self.q)
@@ -1638,7 +1640,7 @@ class Engine:
     def _ode_fwd_multi(self, jobs, t, th, method, H, K, m, zero16=None, **kw):
         """KN.ode_fwd_multi; with dopri5 one kernels.dopri5_fwd per 8 jobs, each job's step record kept for its sweep
         (keyed by the job's sample and grid, which the sweep jobs share)"""
-        if self.tiled:
+        if self.tiled and method != KN.DOPRI5:
             return KN.tiled_ode_fwd_multi(jobs, t, th, method, H, K, m, zero16=zero16, **kw)
         if method != KN.DOPRI5:
             return KN.ode_fwd_multi(jobs, t, th, method, H, K, m, zero16=zero16, **kw)
@@ -1648,25 +1650,26 @@ class Engine:
         for i in range(0, len(jobs), KN.DOPRI5_MAXJOBS):
             part = jobs[i:i + KN.DOPRI5_MAXJOBS]
             recs = KN.dopri5_fwd([dict(xT=j['xT'], start=j['start'], u=j['u'], Y=j.get('Y')) for j in part], t, th, H, K, m,
-                                 self.config['u_hidden_dim'], chunk=o.dopri5_chunk, max_steps=o.dopri5_max_steps)
+                                 self.config['u_hidden_dim'], chunk=o.dopri5_chunk, max_steps=o.dopri5_max_steps,
+                                 stepper=self.dopri5_stepper)
             for j, r in zip(part, recs):
                 self._dopri_recs[(j['xT'].data_ptr(), t.data_ptr())] = r
 
     def _ode_bwd_multi(self, jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, **kw):
         """KN.ode_bwd_multi; with dopri5 kernels.dopri5_sweep over the records of the forward that produced these jobs' u"""
-        if self.tiled:
+        if self.tiled and method != KN.DOPRI5:
             return KN.tiled_ode_bwd_multi(jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint, **kw)
         if method != KN.DOPRI5:
             return KN.ode_bwd_multi(jobs, t, th, method, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, adjoint=adjoint, **kw)
         for i in range(0, len(jobs), KN.DOPRI5_MAXJOBS):
             part = [dict(j, rec=self._dopri_recs[(j['xT'].data_ptr(), t.data_ptr())]) for j in jobs[i:i + KN.DOPRI5_MAXJOBS]]
-            KN.dopri5_sweep(part, t, th, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones)
+            KN.dopri5_sweep(part, t, th, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, stepper=self.dopri5_stepper)
 
     def _u_forward(self, xT, t, start):
-        if self.tiled:
+        if self.tiled and not self.dopri5:
             return KN.tiled_ode_fwd(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, want_Y=False)[0]
         return KN.u_forward(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, self.config['u_hidden_dim'],
-                            chunk=self.options.dopri5_chunk, max_steps=self.options.dopri5_max_steps)
+                            chunk=self.options.dopri5_chunk, max_steps=self.options.dopri5_max_steps, stepper=self.dopri5_stepper)
 
     def predict_group(self, G):
         """u_theta on the interior paths of a loaded group as the module returns it, [N, L, 1] -- no path tensor, no callables:

@@ -472,8 +472,26 @@ def ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_par
 # ----------------------------------------------------------------------------------------------------------------------
 DOPRI5_RTOL, DOPRI5_ATOL = 1e-7, 1e-9      # torchdiffeq's defaults (the reference passes neither)
 DOPRI5_CHUNK, DOPRI5_MAX_STEPS = 8, 10000  # attempts per host check; accepted steps per call (defaults of EngineOptions.dopri5_*)
-DOPRI5_MAXJOBS = 8                         # jobs per launch (csrc/xw_dopri.hip XW_DOPRI_MAXJOBS)
+DOPRI5_MAXJOBS = 8                         # jobs per launch (csrc/xw_dopri_ctl.h XW_DOPRI_MAXJOBS)
+DOPRI5_STEPPERS = ('vector', 'tiled')      # the two implementations: csrc/xw_dopri.hip (the field per path on the vector ALU, up to
+                                           # GENERIC_ODE_MAX) and csrc/xw_tdopri.hip (per 16-path tile on the MFMA, up to TILED_ODE_MAX)
 CTL_T0, CTL_DT, CTL_NACC, CTL_NATT, CTL_DONE, CTL_STATUS, CTL_RATIO, CTL_GAP = 0, 1, 2, 3, 4, 5, 8, 9
+
+
+def dopri5_stepper(name):
+    """`name` if it is one of DOPRI5_STEPPERS (EngineOptions.dopri5_stepper, XNODE.dopri5_stepper), else XnwanError"""
+    if name not in DOPRI5_STEPPERS:
+        raise XnwanError("dopri5_stepper = %r: one of 'vector' (csrc/xw_dopri.hip, the field on the vector ALU, widths up to %s) "
+                         "and 'tiled' (csrc/xw_tdopri.hip, the field on the tiled MFMA stepper, widths up to %s)"
+                         % (name, GENERIC_ODE_MAX, TILED_ODE_MAX))
+    return name
+
+
+def _dopri5_tiled_work(sweep, d, H, K, m, Ns, dev):
+    """the per-launch workspace of the tiled dopri5 kernels for jobs of Ns paths (xw_tdopri5_work doubles per 16-path tile)"""
+    per = lib.xw_tdopri5_work(1 if sweep else 0, d, H, K, m)
+    check(min(per, 0), 'xw_tdopri5_work')
+    return torch.empty(per * sum((N + 15) // 16 for N in Ns), dtype=F64, device=dev)
 
 
 def dopri5_status_message(status, ctl, max_steps):
@@ -500,13 +518,14 @@ class Dopri5Record:
     sizes and the controller.  `n_acc`, `n_att`, `min_gap`, `grid` (host float64 tensor) and `steps` (accepted (t0, dt)) are
     filled when dopri5_fwd returns."""
 
-    def __init__(self, N, H, cap, dev):
-        self.N, self.H, self.cap = N, H, cap
+    def __init__(self, N, H, cap, dev, stepper='vector'):
+        self.N, self.H, self.cap, self.stepper = N, H, cap, dopri5_stepper(stepper)
         self.rec_y = torch.empty(cap + 1, H, N, dtype=F64, device=dev)
         self.rec_t = torch.empty(cap + 1, dtype=F64, device=dev)
         self.rec_h = torch.empty(max(cap, 1), dtype=F64, device=dev)
         self.fbuf = torch.empty(2, H, N, dtype=F64, device=dev)
-        self.work = torch.empty(lib.xw_dopri5_work_size(N), dtype=F64, device=dev)
+        # (the partial sums of the forward's reductions: per 64-path block, or per 16-path tile -- the sweeps do not read them)
+        self.work = torch.empty((lib.xw_tdopri5_part_size if stepper == 'tiled' else lib.xw_dopri5_work_size)(N), dtype=F64, device=dev)
         self.n_acc = self.n_att = 0
         self.grid = self.min_gap = self.steps = None
 
@@ -523,14 +542,16 @@ class Dopri5Record:
 
 
 def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS,
-               cap=None):
+               cap=None, stepper='vector'):
     """u_theta with solver 'dopri5' for jobs = list of dicts(xT[d,N], start[N], u[L,N], Y[L,H,N] or None) sharing t and theta;
     one step size per job (one odeint call of the reference).  Hn: the network's u_hidden_dim (the RMS norms divide by N Hn).
     Enqueues the init launches, then attempts in chunks of `chunk` launches; after each chunk the controllers are copied to
     page-locked host memory and ONE event is waited on; the records grow on the host before the next chunk, so that no attempt
     can write past them.  Returns a Dopri5Record per job (for dopri5_sweep and diagnostics).  A controller that ends with a bad
-    status raises XnwanError.  Synchronises with the host: a dopri5 forward cannot be captured into a graph."""
+    status raises XnwanError.  Synchronises with the host: a dopri5 forward cannot be captured into a graph.
+    stepper: 'vector' (xw_dopri5_*) or 'tiled' (xw_tdopri5_*: H, K up to 256, m up to 32; one workspace for all its launches)."""
     _need_gpu()
+    tiled = dopri5_stepper(stepper) == 'tiled'
     if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
         raise XnwanError('dopri5_fwd: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
     chunk, max_steps = int(chunk), int(max_steps)
@@ -548,8 +569,9 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
         N = j['xT'].shape[1]
         _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
         _chk(j.get('Y'), F64, (L, H, N), 'Y')
-        recs.append(Dopri5Record(N, H, int(cap) if cap else 4 * chunk, dev))
+        recs.append(Dopri5Record(N, H, int(cap) if cap else 4 * chunk, dev, stepper))
     arr = (XwDopriJob * nj)()
+    work = _dopri5_tiled_work(False, d, H, K, m, [r.N for r in recs], dev) if tiled else None
 
     def fill():
         for i, (a, j, r) in enumerate(zip(arr, jobs, recs)):
@@ -558,7 +580,10 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
             a.ctl, a.work, a.N, a.cap = _p(ctl[i]), _p(r.work), r.N, r.cap
     args = (_p(t), _p(theta), L, d, H, K, m, int(Hn), float(rtol), float(atol))
     fill()
-    check(lib.xw_dopri5_init(arr, nj, *args, _stream()), 'xw_dopri5_init')
+    if tiled:
+        check(lib.xw_tdopri5_init(arr, nj, *args, _p(work), _stream()), 'xw_tdopri5_init')
+    else:
+        check(lib.xw_dopri5_init(arr, nj, *args, _stream()), 'xw_dopri5_init')
     ev = torch.cuda.Event()
     n_acc = [0] * nj
     while True:
@@ -569,7 +594,10 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
                 grown = True
         if grown:
             fill()
-        check(lib.xw_dopri5_attempts(arr, nj, *args, max_steps, chunk, _stream()), 'xw_dopri5_attempts')
+        if tiled:
+            check(lib.xw_tdopri5_attempts(arr, nj, *args, max_steps, chunk, _p(work), _stream()), 'xw_tdopri5_attempts')
+        else:
+            check(lib.xw_dopri5_attempts(arr, nj, *args, max_steps, chunk, _stream()), 'xw_dopri5_attempts')
         mirror.copy_(ctl, non_blocking=True)
         ev.record()
         ev.synchronize()
@@ -588,23 +616,25 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
     return recs
 
 
-def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS):
+def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS, stepper='vector'):
     """u[L,N] of one group with any served solver: ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
-    Hn: the network's u_hidden_dim (dopri5's RMS norms)"""
+    Hn: the network's u_hidden_dim (dopri5's RMS norms); stepper: dopri5's implementation (DOPRI5_STEPPERS)"""
     if method != DOPRI5:
         if stepper_family(H, K, m, method=method) == 'tiled':
             return tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
         return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
     u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)
-    dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps)
+    dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps, stepper=stepper)
     return u
 
 
-def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False):
+def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False, stepper='vector'):
     """reverse of the accepted steps of dopri5_fwd (step sizes and grid as constants: DESIGN 8).  jobs: list of dicts as for
     ode_bwd_multi (xT, start, ubar or res, gx, gs, gslab; no Y / act) plus 'rec': the job's Dopri5Record.  Same outputs and
-    layouts as ode_bwd_multi (mode bits 0..2)."""
+    layouts as ode_bwd_multi (mode bits 0..2).  stepper: 'vector' (xw_dopri5_sweep) or 'tiled' (xw_tdopri5_sweep); either reverses
+    a record of either forward at widths both serve."""
     _need_gpu()
+    tiled = dopri5_stepper(stepper) == 'tiled'
     if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
         raise XnwanError('dopri5_sweep: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
     if x_cot_ones and not (want_x and want_params):
@@ -630,7 +660,11 @@ def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False)
         _set_res(b, j, L, N)
         a.rec_y, a.rec_t, a.rec_h, a.ctl = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.ctl)
     mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0)
-    check(lib.xw_dopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _stream()), 'xw_dopri5_sweep')
+    if tiled:
+        work = _dopri5_tiled_work(True, d, H, K, m, [a.b.N for a in arr], t.device)
+        check(lib.xw_tdopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _p(work), _stream()), 'xw_tdopri5_sweep')
+    else:
+        check(lib.xw_dopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _stream()), 'xw_dopri5_sweep')
 
 
 DISC_UNROLLED_DEPTH = 9   # v_layers of the reference's YAML: the depth the recomputing reverse kernels are compiled for

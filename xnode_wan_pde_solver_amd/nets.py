@@ -172,7 +172,8 @@ class _Dopri5Fn(torch.autograd.Function):
         N, L = X.shape[0], X.shape[1]
         u = torch.empty(L, N, dtype=F64, device=X.device)
         rec, = KN.dopri5_fwd([dict(xT=xT, start=s, u=u)], t, blob.data, net.kdims[0], net.kdims[1], net.num_layers,
-                             net.hidden_dim, rtol=net.rtol, atol=net.atol, chunk=net.dopri5_chunk, max_steps=net.dopri5_max_steps)
+                             net.hidden_dim, rtol=net.rtol, atol=net.atol, chunk=net.dopri5_chunk, max_steps=net.dopri5_max_steps,
+                             stepper=net.dopri5_stepper)
         net.last_dopri5 = rec
         ctx.net, ctx.rec, ctx.x_dtype, ctx.s_shape, ctx.s_dtype = net, rec, X.dtype, start.shape, start.dtype
         ctx.save_for_backward(xT, t, s)
@@ -189,7 +190,7 @@ class _Dopri5Fn(torch.autograd.Function):
         gslab = torch.empty(KN.ode_bwd_slabs(N), KN.theta_size(d, H, K), dtype=F64, device=gu.device) if want_p else None
         ubar = gu.squeeze(2).t().contiguous().to(F64)
         KN.dopri5_sweep([dict(xT=xT, start=s, ubar=ubar, gx=gx, gs=gs, gslab=gslab, rec=ctx.rec)], t, net.blob.data, H, K,
-                        net.num_layers, want_x=True, want_params=want_p)
+                        net.num_layers, want_x=True, want_params=want_p, stepper=net.dopri5_stepper)
         gX = None
         if ctx.needs_input_grad[0]:
             gX = torch.zeros((N, t.shape[0], d + 1), dtype=ctx.x_dtype, device=gu.device)
@@ -264,6 +265,7 @@ class XNODE(nn.Module):
             raise XnwanError(ADAMS_ADJOINT_REFUSED)
         self.rtol, self.atol = KN.DOPRI5_RTOL, KN.DOPRI5_ATOL        # (dopri5: torchdiffeq's defaults, as the reference gets them)
         self.dopri5_chunk, self.dopri5_max_steps = KN.DOPRI5_CHUNK, KN.DOPRI5_MAX_STEPS
+        self.dopri5_stepper = 'vector'                               # (or 'tiled': kernels.DOPRI5_STEPPERS, EngineOptions.dopri5_stepper)
         self._ode_fn = _Dopri5Fn if self.method == KN.DOPRI5 else _OdeFn
         self.initial_layers = nn.Sequential(nn.Linear(1, hidden_dim), nn.ReLU(), nn.Linear(hidden_dim, hidden_dim),
                                             nn.ReLU(), nn.Linear(hidden_dim, hidden_dim)).double()
@@ -279,11 +281,12 @@ class XNODE(nn.Module):
         self.to(device)
         H, K, d = self.hidden_dim, self.hidden_hidden_dim, self.setup['dim']
         self.family = KN.stepper_family(H, K, self.num_layers, method=self.method)
-        if self.family == 'tiled' and self.method == KN.DOPRI5:
+        if self.family == 'tiled' and self.method == KN.DOPRI5 and KN.dopri5_stepper(self.dopri5_stepper) != 'tiled':
             raise XnwanError("solver 'dopri5' runs on the generic path's field code, up to u_hidden_dim %d / u_hidden_hidden_dim %d / "
                              "u_layers %d; u_hidden_dim = %d, u_hidden_hidden_dim = %d, u_layers = %d need the tiled stepper family, "
-                             "which runs the fixed-grid solvers %s only" % (KN.GENERIC_ODE_MAX + (KN.GENERIC_ODE_MAX_DEPTH, H, K, self.num_layers,
-                                                                              sorted(KN.METHODS))))
+                             "which runs the fixed-grid solvers %s only -- unless dopri5_stepper = 'tiled' (XNODE.dopri5_stepper, "
+                             "EngineOptions.dopri5_stepper, XW_DOPRI5_STEPPER) selects dopri5's implementation on that family"
+                             % (KN.GENERIC_ODE_MAX + (KN.GENERIC_ODE_MAX_DEPTH, H, K, self.num_layers, sorted(KN.METHODS))))
         # (the tiled family: the network's own widths, the generic layout)
         self.kdims = KN.stepper_kdims(H, K, self.num_layers, method=self.method)
         slots, total = _u_slots(d, H, K, self.kdims[0], self.kdims[1], self.num_layers > 1)

@@ -64,6 +64,8 @@ class EngineOptions:
     # ---- solver 'dopri5' (kernels.dopri5_fwd) ------------------------------------------------------------------------------------
     dopri5_chunk: int = 8               # XW_DOPRI5_CHUNK: attempt launches enqueued between two read-backs of the step controllers
     dopri5_max_steps: int = 10000       # XW_DOPRI5_MAX_STEPS: accepted steps per forward before XnwanError
+    dopri5_stepper: str = 'vector'      # XW_DOPRI5_STEPPER: 'vector' (csrc/xw_dopri.hip: the field per path on the vector ALU, up to (64, 16)) or
+                                        # 'tiled' (csrc/xw_tdopri.hip: the field on the tiled family's MFMA layout, up to 256 x 256, u_layers 32)
     # ---- several GPUs (dist.World) ------------------------------------------------------------------------------------------
     replicate_below: int = 16           # XW_REPLICATE_BELOW: groups with fewer paths per rank are computed whole on every rank
     native_allreduce: bool = True       # XW_NATIVE_ALLREDUCE: the exchange through xw_allreduce (RCCL) instead of torch.distributed
@@ -109,6 +111,7 @@ class EngineOptions:
         o.show_plan = _flag('XW_SHOW_PLAN', o.show_plan)
         o.dopri5_chunk = _int('XW_DOPRI5_CHUNK', o.dopri5_chunk)
         o.dopri5_max_steps = _int('XW_DOPRI5_MAX_STEPS', o.dopri5_max_steps)
+        o.dopri5_stepper = os.environ.get('XW_DOPRI5_STEPPER') or o.dopri5_stepper
         o.replicate_below = _int('XW_REPLICATE_BELOW', o.replicate_below)
         o.native_allreduce = _flag('XW_NATIVE_ALLREDUCE', o.native_allreduce)
         return o

@@ -236,6 +236,7 @@ class NODE_WAN_solver:
         s = self.setup
         self.u_net, self.v_net = build_networks(self.config, s, func_h, func_g, self.domain)
         with torch.cuda.device(self.device):
+            self.u_net.module.dopri5_stepper = opt.dopri5_stepper
             self.u_net.module.bind(self.device)
             self.v_net.module.bind(self.device)
             funcs = dict(a=func_a, b=func_b, c=func_c, h=func_h, f=func_f, g=func_g)
@@ -249,6 +250,7 @@ class NODE_WAN_solver:
 
     def rebind(self):
         """re-alias the parameters to fresh blobs after the modules were moved or cast"""
+        self.u_net.module.dopri5_stepper = self.options.dopri5_stepper
         self.u_net.module.bind(self.device)
         self.v_net.module.bind(self.device)
         self.engine.theta, self.engine.phi = self.u_net.module.blob, self.v_net.module.blob
@@ -441,7 +443,7 @@ class NODE_WAN_solver:
                 s_k, a_k = next(starts)
                 u = KN.u_forward(x[:, 0, 1:].t().contiguous(), x[0, :, 0].contiguous(), s_k.contiguous(), net.blob.data, net.method,
                                  net.kdims[0], net.kdims[1], net.num_layers, net.hidden_dim, chunk=self.options.dopri5_chunk,
-                                 max_steps=self.options.dopri5_max_steps)
+                                 max_steps=self.options.dopri5_max_steps, stepper=self.options.dopri5_stepper)
                 out = u.t().unsqueeze(2).contiguous()               # [N, L, 1] like xnwan::xnode_forward
                 return out[:, 0, :] if (x.shape[1] == 1 and a_k) else out   # (src/model.py:89-91: [N, 1] on a single slice at T0)
             return L_norm(Xs, u_fn, self.p, lambda x: next(sols), volume, self.setup['N_r'])
@@ -472,7 +474,10 @@ class NODE_WAN_solver:
             'sub_steps': 'captured HIP graphs' if (cube and eng.use_graphs) else ('one C call per group sub-step (xw_substep_*)' if eng.use_runner and
                                                                                  eng.structure.c_kappa is not None else 'launch by launch'),
             'ode_solver': ("dopri5 (adaptive, step sizes chosen on the device per group; its sub-steps run as eager launches, "
-                           "controllers read back every %d attempts)" % self.options.dopri5_chunk if eng.dopri5 else
+                           "controllers read back every %d attempts; dopri5_stepper = '%s': %s)"
+                           % (self.options.dopri5_chunk, eng.dopri5_stepper,
+                              'the field on the tiled MFMA stepper, csrc/xw_tdopri.hip' if eng.dopri5_stepper == 'tiled' else
+                              'the field per path on the vector ALU, csrc/xw_dopri.hip') if eng.dopri5 else
                            '%s (fixed grid: the sample times%s)' % (self.config['solver'], ', Adams-Bashforth AB3 .. AB11 after two rk4 '
                                                                      'start-up steps' if self.config['solver'] == 'explicit_adams' else '')),
             'stepper': {'mfma': 'fused MFMA container %s' % ((eng.H, eng.K),), 'generic': 'generic vector-ALU path (csrc/xw_generic.hip)',
