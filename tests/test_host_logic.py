@@ -132,6 +132,34 @@ def test_cabi_exports_match_header():
     assert _lib.lib.xw_theta_size(20, 20, 10) == 1651 and _lib.lib.xw_phi_size(20, 50) == 3701
 
 
+# xw_ode_act_rows(method, H, K, m) for m = 1..10, read once from the library of the commit BEFORE (64, 16) joined the list of
+# containers in xw_ode_abi.hip (ctypes calls on that build; nothing here comes from the code under test)
+ACT_ROWS_PINNED = {
+    (0, 20, 10): [12, 22, 32, 42, 52, 62, 72, 82, 92, 102],
+    (0, 32, 12): [14, 26, 38, 50, 62, 74, 86, 98, 110, 122],
+    (0, 64, 16): [18, 34, 50, 66, 82, 98, 114, 130, 146, 164],
+    (1, 20, 10): [44, 64, 84, 104, 124, 144, 164, 184, 204, 224],
+    (1, 32, 12): [60, 84, 108, 132, 156, 180, 204, 228, 252, 276],
+    (1, 64, 16): [100, 132, 164, 196, 228, 260, 292, 324, 356, 392],
+    (2, 20, 10): [0] * 10,
+    (2, 32, 12): [0] * 10,
+    (2, 64, 16): [0] * 10,
+}
+# ... the same for every method 0, 1, 2: (H, K, m) -> rows.  Deeper fields and other widths run on the generic path (0: the sweeps
+# recompute); what the generic path refuses too is XW_E_DIMS = -1
+ACT_ROWS_PINNED_ANY_METHOD = {(64, 16, 11): 0, (48, 16, 8): 0, (20, 10, 11): 0, (20, 10, 12): 0, (65, 16, 8): -1, (64, 16, 0): -1,
+                              (64, 16, 33): -1, (20, 10, 0): -1, (20, 10, 33): -1}
+
+
+def test_activation_rows_are_those_of_the_hand_written_wide_branch():
+    rows = _lib.lib.xw_ode_act_rows
+    for (method, H, K), want in ACT_ROWS_PINNED.items():
+        assert [rows(method, H, K, m) for m in range(1, 11)] == want, (method, H, K)
+    for method in (0, 1, 2):
+        for (H, K, m), want in ACT_ROWS_PINNED_ANY_METHOD.items():
+            assert rows(method, H, K, m) == want, (method, H, K, m)
+
+
 def test_no_gpu_means_loud_failure():
     if torch.cuda.is_available():
         pytest.skip('GPU present')

@@ -12,6 +12,12 @@
 //
 // Memory traffic per path: x (d floats) once, the checkpoint y[L,H] written once / read once, u[L] -- everything else
 // stays on chip.  At the headline size this kernel is bound by the FP64 matrix pipe, not by HBM.
+//
+// This file is the shared core (tableaux, job tables, cotangent forms, activation store, k_ode_fwd, sweep_body, sweep_tail, kernels,
+// entry points).  What depends on the matrix instruction the FIELD runs on -- operands, evaluation, vector-Jacobian product, the duo
+// sweep's partner wave, the sweep launcher -- is one of two headers, included in three sections (XW_ODE_SECTION, undefined by the header):
+//   xw_ode_mfma4.h   v_mfma_f64_4x4x4    the narrow containers (20, 10) and (32, 12), with the narrow tiles of xw_ode_n4.h
+//   xw_ode_mfma16.h  v_mfma_f64_16x16x4  the wide container (64, 16), -DXW_ODE_WIDE16
 #include <cstdlib>
 #include <type_traits>
 #include "xw_common.h"
@@ -26,6 +32,11 @@
 #if !defined(XW_ODE_H) || !defined(XW_ODE_K)
 #error "compile with -DXW_ODE_H=<u_hidden_dim> -DXW_ODE_K=<u_hidden_hidden_dim>"
 #endif
+#ifdef XW_ODE_WIDE16
+#define XW_ODE_FORM "xw_ode_mfma16.h"
+#else
+#define XW_ODE_FORM "xw_ode_mfma4.h"
+#endif
 #define XW_CAT4_(a, b, c, d) a##b##c##d
 #define XW_CAT4(a, b, c, d) XW_CAT4_(a, b, c, d)
 #define XW_ODE_FN(name) XW_CAT4(name, XW_ODE_H, _, XW_ODE_K)
@@ -33,21 +44,6 @@
 #define XW_ODE_DISPATCH(CALL)                                    \
   switch (m) {                                                   \
     case XW_ODE_ONLY_M: { CALL(XW_ODE_H, XW_ODE_K, XW_ODE_ONLY_M) } \
-    default: return XW_E_DIMS;                                   \
-  }
-#elif defined(XW_ODE_WIDE16)     /* (4 (m - 1) ReLU-mask bits per stage: one 32-bit word up to depth 9, two at depth 10 -- SaveX) */
-#define XW_ODE_DISPATCH(CALL)                                    \
-  switch (m) {                                                   \
-    case 1: { CALL(XW_ODE_H, XW_ODE_K, 1) }                      \
-    case 2: { CALL(XW_ODE_H, XW_ODE_K, 2) }                      \
-    case 3: { CALL(XW_ODE_H, XW_ODE_K, 3) }                      \
-    case 4: { CALL(XW_ODE_H, XW_ODE_K, 4) }                      \
-    case 5: { CALL(XW_ODE_H, XW_ODE_K, 5) }                      \
-    case 6: { CALL(XW_ODE_H, XW_ODE_K, 6) }                      \
-    case 7: { CALL(XW_ODE_H, XW_ODE_K, 7) }                      \
-    case 8: { CALL(XW_ODE_H, XW_ODE_K, 8) }                      \
-    case 9: { CALL(XW_ODE_H, XW_ODE_K, 9) }                      \
-    case 10: { CALL(XW_ODE_H, XW_ODE_K, 10) }                    \
     default: return XW_E_DIMS;                                   \
   }
 #else
@@ -115,53 +111,8 @@ template <int H, int K> struct Dim {
   __device__ static constexpr int HR(int ht) { return (H - 16 * ht) >= 16 ? 4 : (H - 16 * ht + 3) / 4; }        // rows of y
   __device__ static constexpr int HR1(int ct) { return (H + 1 - 16 * ct) >= 16 ? 4 : (H + 1 - 16 * ct + 3) / 4; }  // + time row
   static constexpr int CT = (H + 16) / 16;   // 16-row tiles of [y ; t]: the time row H is its own tile when H % 16 == 0
-#ifndef XW_ODE_WIDE16
-  static_assert(K <= 15, "row K of the 16-row K-tile is the ones row that collects the bias gradients");
-  static_assert(HT <= 2 && CT <= 3, "H <= 32");
-#else
-  // the wide container (round 6, -DXW_ODE_WIDE16): whole 16-row tiles on v_mfma_f64_16x16x4 (the wide field family below), bias
-  // gradients as row sums -- no ones row, no 4x4 blocks, no narrow tiles; a duo sweep of its own (duo_outer below)
-  static_assert(K == 16 && H % 16 == 0 && H <= 64, "the wide container: K = 16, H a multiple of 16 up to 64");
-#endif
 };
 
-#ifndef XW_ODE_WIDE16
-// The field's layers run on v_mfma_f64_4x4x4_4b_f64: one instruction = a 4x4 weight block times 4 rows x 16 paths of
-// the chain layout (its four "blocks" are the four groups of 4 paths; the weight block is replicated over them -- the
-// CBSZ/ABID broadcast does nothing on the f64 form, profiles/r02_probe_mfma4b.txt).  A [K x K] layer is KB x KB = 9
-// instructions of 18 clocks on KB INDEPENDENT accumulators instead of 3 dependent 16x16x4 instructions of 64 + 17 clocks
-// on a tile with 10 of 16 rows live: 185 instead of 276 clocks per layer for the lone wave of a stepper tile, 16 % less
-// matrix-pipe time when the chip is shared (same probe).
-template <int H, int K> struct FieldW {      // forward operands: 4x4 blocks (row block, k block)
-  double Wy[Dim<H, K>::KB][Dim<H, K>::HB];   // Win[:, d+1:]  [K x H]
-  double Wh[Dim<H, K>::KB][Dim<H, K>::KB];   // Wh            [K x K]
-  double Wo[Dim<H, K>::HB][Dim<H, K>::KB];   // Wo            [H x K]
-  d4 wt, bh;                                 // Win[:, d] (time column), Wh.b
-  d4 bo[Dim<H, K>::HT];                      // Wo.b
-};
-template <int H, int K> struct FieldWT {     // transposed operands for the vector-Jacobian product
-  double WyT[Dim<H, K>::HB][Dim<H, K>::KB];  // [H x K]
-  double WhT[Dim<H, K>::KB][Dim<H, K>::KB];  // [K x K]
-  double WoT[Dim<H, K>::KB][Dim<H, K>::HB];  // [K x H]
-};
-#else
-// ---- the wide container: the field on v_mfma_f64_16x16x4 -------------------------------------------------------------------
-// K = 16 and H = 16 HT are whole 16-row tiles, so the 16x16x4 form wastes nothing (at K = 10 it ran 10 of 16 rows): a [K x K]
-// layer is 4 chained instructions, Win's y-part H / 4, Wo HT x 4.  An A-fragment is ONE double per lane and (tile, k-step):
-// 16 + 4 + 4 HT doubles hold the whole field (as 4x4 blocks replicated over the lane blocks it would be 144 doubles at (64, 16)).
-template <int H, int K> struct FieldW {
-  double Wy[Dim<H, K>::KSH];                   // Win[:, d+1:]  [K x H], k-steps over H
-  double Wh[Dim<H, K>::KSK];                   // Wh            [K x K]
-  double Wo[Dim<H, K>::HT][Dim<H, K>::KSK];    // Wo            [H x K], row tiles x k-steps over K
-  d4 wt, bh;
-  d4 bo[Dim<H, K>::HT];
-};
-template <int H, int K> struct FieldWT {
-  double WoT[Dim<H, K>::KSH];                  // (Wo^T) [K x H]
-  double WhT[Dim<H, K>::KSK];                  // (Wh^T) [K x K]
-  double WyT[Dim<H, K>::HT][Dim<H, K>::KSK];   // (Wy^T) [H x K]
-};
-#endif
 template <int M> struct Save {               // what the VJP of one field evaluation needs
   d4 z[M > 1 ? M - 1 : 1];                   // relu(z_0) .. relu(z_{m-2}): layer inputs; their sign pattern is the ReLU mask
   d4 a;                                      // tanh(z_{m-1})
@@ -176,7 +127,7 @@ template <int M> struct Save {               // what the VJP of one field evalua
 // feeds EXACT zeros (+0, the biases start at zero) to the next one, and relu'(+0) = 0 in the reference (torch) -- with sign
 // bits the boundary sweep of the d = 20 fixture was off by 5e-5.
 #define XW_KB ((XW_ODE_K + 3) / 4)
-// (more than 32 bits -- the wide container at depth 10: 36 -- take a second word, bits_hi = bits 32 and up; XW_MASK_WORDS)
+// (more than 32 bits -- the wide container, 4 (m - 1) bits per stage, at depth 10: 36 -- take a second word, bits_hi = bits 32 and up; XW_MASK_WORDS)
 #define XW_MASK_WORDS(M) ((XW_KB * ((M) - 1) > 32) ? 2 : 1)
 template <int M> struct SaveX {
   static_assert(XW_KB * (M - 1) <= 64, "mask words");
@@ -193,79 +144,8 @@ template <int M> struct SaveX {
   }
 };
 
-#ifndef XW_ODE_WIDE16
-template <int H, int K>
-__device__ __forceinline__ void load_field(const double* __restrict__ th, const UOff& o, int d, FieldW<H, K>& w) {
-  typedef Dim<H, K> D;
-  const double* Wy = th + o.Win + d + 1;
-#pragma unroll
-  for (int rb = 0; rb < D::KB; ++rb) {
-#pragma unroll
-    for (int kb = 0; kb < D::HB; ++kb) w.Wy[rb][kb] = xw_fragA4(Wy, o.ldin, K, H, 4 * rb, 4 * kb);
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) w.Wh[rb][kb] = xw_fragA4(th + o.Wh, K, K, K, 4 * rb, 4 * kb);
-  }
-#pragma unroll
-  for (int rb = 0; rb < D::HB; ++rb)
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) w.Wo[rb][kb] = xw_fragA4(th + o.Wo, K, H, K, 4 * rb, 4 * kb);
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) w.bo[ht] = xw_vecD(th + o.Wob, H, 16 * ht);
-  w.wt = xw_vecD_strided(th + o.Win + d, o.ldin, K, 0);
-  w.bh = xw_vecD(th + o.Whb, K, 0);
-}
-template <int H, int K>
-__device__ __forceinline__ void load_field_T(const double* __restrict__ th, const UOff& o, int d, FieldWT<H, K>& w) {
-  typedef Dim<H, K> D;
-  const double* Wy = th + o.Win + d + 1;
-#pragma unroll
-  for (int rb = 0; rb < D::HB; ++rb)
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) w.WyT[rb][kb] = xw_fragAT4(Wy, o.ldin, K, H, 4 * rb, 4 * kb);
-#pragma unroll
-  for (int rb = 0; rb < D::KB; ++rb) {
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) w.WhT[rb][kb] = xw_fragAT4(th + o.Wh, K, K, K, 4 * rb, 4 * kb);
-#pragma unroll
-    for (int kb = 0; kb < D::HB; ++kb) w.WoT[rb][kb] = xw_fragAT4(th + o.Wo, K, H, K, 4 * rb, 4 * kb);
-  }
-}
-
-#else
-template <int H, int K>
-__device__ __forceinline__ void load_field(const double* __restrict__ th, const UOff& o, int d, FieldW<H, K>& w) {
-  typedef Dim<H, K> D;
-  const double* Wy = th + o.Win + d + 1;
-#pragma unroll
-  for (int ks = 0; ks < D::KSH; ++ks) w.Wy[ks] = xw_fragA(Wy, o.ldin, K, H, 0, 4 * ks);
-#pragma unroll
-  for (int ks = 0; ks < D::KSK; ++ks) w.Wh[ks] = xw_fragA(th + o.Wh, K, K, K, 0, 4 * ks);
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) w.Wo[ht][ks] = xw_fragA(th + o.Wo, K, H, K, 16 * ht, 4 * ks);
-    w.bo[ht] = xw_vecD(th + o.Wob, H, 16 * ht);
-  }
-  w.wt = xw_vecD_strided(th + o.Win + d, o.ldin, K, 0);
-  w.bh = xw_vecD(th + o.Whb, K, 0);
-}
-template <int H, int K>
-__device__ __forceinline__ void load_field_T(const double* __restrict__ th, const UOff& o, int d, FieldWT<H, K>& w) {
-  typedef Dim<H, K> D;
-  const double* Wy = th + o.Win + d + 1;
-#pragma unroll
-  for (int ks = 0; ks < D::KSH; ++ks) w.WoT[ks] = xw_fragAT(th + o.Wo, K, H, K, 0, 4 * ks);          // (Wo^T)[i][4 ks + k] = Wo[4 ks + k][i]
-#pragma unroll
-  for (int ks = 0; ks < D::KSK; ++ks) w.WhT[ks] = xw_fragAT(th + o.Wh, K, K, K, 0, 4 * ks);
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht)
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) w.WyT[ht][ks] = xw_fragAT(Wy, o.ldin, K, H, 16 * ht, 4 * ks);   // (Wy^T)[16 ht + i][4 ks + k] = Wy[4 ks + k][16 ht + i]
-}
-
-#endif
-// F([x, t, y]) of src/model.py:153-156: z0 = Win [x;t;y] + b (x part pre-contracted into xp), (m-1) tied ReLU layers,
-// tanh, output layer.  y/out: HT chain tiles.
+// F([x, t, y]) of src/model.py:153-156 (field_fwd of the form header): z0 = Win [x;t;y] + b (x part pre-contracted into xp),
+// (m-1) tied ReLU layers, tanh, output layer.  y/out: HT chain tiles.
 // Where the layer inputs of an evaluation go: nowhere, into registers (Save), or straight to the activation store.
 struct SinkNone {
   __device__ __forceinline__ void fence() const {}
@@ -280,98 +160,6 @@ template <int M> struct SinkSave {
   __device__ __forceinline__ void z(int j, d4 r) const { sv.z[j] = r; }
   __device__ __forceinline__ void a(d4 v) const { sv.a = v; }
 };
-#ifndef XW_ODE_WIDE16
-template <int H, int K, int M, bool OUT = true, class Sink>
-__device__ __forceinline__ void field_fwd(const FieldW<H, K>& w, double t, d4 xp, const d4 (&y)[Dim<H, K>::HT],
-                                          d4 (&out)[Dim<H, K>::HT], const Sink& sink) {
-  typedef Dim<H, K> D;
-  // (k block outer, row block inner: consecutive instructions write different accumulators)
-  d4 z = xw_zero4();
-#pragma unroll
-  for (int r = 0; r < D::KB; ++r) z[r] = fma(w.wt[r], t, xp[r]);
-#pragma unroll
-  for (int kb = 0; kb < D::HB; ++kb)
-#pragma unroll
-    for (int rb = 0; rb < D::KB; ++rb) z[rb] = XW_MFMA4(w.Wy[rb][kb], y[kb >> 2][kb & 3], z[rb]);
-#pragma unroll
-  for (int j = 0; j < M - 1; ++j) {
-    d4 r = xw_zero4();
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) r[kb] = sink.relu(j, kb, z[kb]);
-    sink.fence();
-    sink.z(j, r);
-    d4 nz = w.bh;
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb)
-#pragma unroll
-      for (int rb = 0; rb < D::KB; ++rb) nz[rb] = XW_MFMA4(w.Wh[rb][kb], r[kb], nz[rb]);
-    z = nz;
-  }
-  d4 a = xw_zero4();
-#pragma unroll
-  for (int kb = 0; kb < D::KB; ++kb) a[kb] = xw_tanh(z[kb]);
-  sink.a(a);
-  if (!OUT) return;
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) out[ht] = w.bo[ht];
-#pragma unroll
-  for (int kb = 0; kb < D::KB; ++kb)
-#pragma unroll
-    for (int rb = 0; rb < D::HB; ++rb) out[rb >> 2][rb & 3] = XW_MFMA4(w.Wo[rb][kb], a[kb], out[rb >> 2][rb & 3]);
-}
-
-#else
-template <int H, int K, int M, bool OUT = true, class Sink>
-__device__ __forceinline__ void field_fwd(const FieldW<H, K>& w, double t, d4 xp, const d4 (&y)[Dim<H, K>::HT],
-                                          d4 (&out)[Dim<H, K>::HT], const Sink& sink) {
-  typedef Dim<H, K> D;
-  d4 z;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) z[r] = fma(w.wt[r], t, xp[r]);
-#pragma unroll
-  for (int ks = 0; ks < D::KSH; ++ks) z = XW_MFMA(w.Wy[ks], y[ks >> 2][ks & 3], z);
-#pragma unroll
-  for (int j = 0; j < M - 1; ++j) {
-    d4 r;
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb) r[kb] = sink.relu(j, kb, z[kb]);
-    sink.fence();
-    sink.z(j, r);
-    d4 nz = w.bh;
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) nz = XW_MFMA(w.Wh[ks], r[ks], nz);
-    z = nz;
-  }
-  d4 a;
-#pragma unroll
-  for (int kb = 0; kb < D::KB; ++kb) a[kb] = xw_tanh(z[kb]);
-  sink.a(a);
-  if (!OUT) return;
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-    out[ht] = w.bo[ht];
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) out[ht] = XW_MFMA(w.Wo[ht][ks], a[ks], out[ht]);
-  }
-}
-
-#endif
-// parameter-gradient accumulators of the field (chain-layout tiles of the gradient matrices)
-#ifndef XW_ODE_WIDE16
-template <int H, int K> struct FieldG {
-  d4 Wh;                                          // rows K, cols K (+ column K = bias via a ones row)
-  d4 Wy[Dim<H, K>::CT];                           // rows K, cols H (+ column H = time column)
-  d4 Wo[Dim<H, K>::HT];                           // rows H, cols K (+ column K = bias)
-};
-#else
-template <int H, int K> struct FieldG {           // wide container: no ones row / time row -- their gradients are elementwise sums
-  d4 Wh;                                          // rows K, cols K
-  d4 Wy[Dim<H, K>::CT];                           // rows K, cols H (tiles 0 .. HT-1; the last entry is not used)
-  d4 Wo[Dim<H, K>::HT];                           // rows H, cols K
-  d4 bh, wt;                                      // sum over evaluations of cot(z_{j+1}) (Wh.b) and of t cot(z_0) (Win's time column), per path
-  d4 bo[Dim<H, K>::HT];                           // ... of cot(out) (Wo.b)
-};
-#endif
 
 // D[i][j] += sum over the 16 paths of Q[i][path] * R[j][path]
 // The block is exactly ONE wave and the LDS executes a wave's DS instructions in issue order, so the transposing
@@ -431,9 +219,6 @@ __device__ __forceinline__ void set_row(d4& q, int row, double v) {
   if ((xw_lane() >> 4) == (row & 3)) q[row >> 2] = v;
 }
 
-// vector-Jacobian product of one field evaluation.  ob: cotangent of F's output; returns the cotangent of the y input
-// in yb, adds the cotangent of z0 into xpb (= cotangent of the x-projection and of Win.b), and (PARAMS) accumulates the
-// parameter gradients.
 // The two halves of an outer product, so that the chain's next matrix instructions can be issued between the LDS
 // stores and the loads that read them back transposed: the lone wave has nothing else to cover that round trip with.
 template <int QR, int RR>
@@ -488,192 +273,14 @@ __device__ __forceinline__ void outer_fire(d4& acc, const double (&a)[4], const 
 
 // vector-Jacobian product of one field evaluation.  ob: cotangent of F's output; returns the cotangent of the y input
 // in yb, adds the cotangent of z0 into xpb (= cotangent of the x-projection and of Win.b), and (PARAMS) accumulates the
-// parameter gradients (outer products over the 16 paths; a row of ones / the time row in the R tile makes the bias and
+// parameter gradients (outer products over the 16 paths; in the 4x4x4 form a row of ones / the time row in the R tile makes the bias and
 // time-column gradients ride along as an extra accumulator column).
 // OUTER: 0 = no weight gradients, 1 = this wave forms them itself (outer products through its own LDS tiles),
 //        2 = "duo" sweep: this wave only posts the cotangent tiles (transposed) into `lds` = the evaluation's Q buffer
 //            (DuoPlan), a partner wave of the block contracts them with the activations it loads itself.
-#ifdef XW_ODE_WIDE16
-// (wide container: every Q tile is a full 16-row tile of the 16x16x4 form -- cot(out) x HT, cot(z_{j+1}) for j = M-2 .. 0, cot(z_0))
-template <int H, int K, int M> struct DuoPlan {
-  static constexpr int HT = Dim<H, K>::HT;
-  static constexpr int NQ = HT + M;
-  __device__ static constexpr int off(int t) { return t * XW_TTILE; }
-  static constexpr int BUF = NQ * XW_TTILE;
-  static_assert(BUF >= 3 * XW_TTILE, "the chain wave's epilogue borrows a buffer for its three transpose tiles");
-};
-#else
-template <int H, int K, int M> struct DuoPlan {
-  static constexpr int HT = Dim<H, K>::HT;
-  static constexpr int NQ = HT + (M - 1) + 1;     // Q tiles of one field evaluation: cot(out) x HT, cot(z_{j+1}) for j = M-2 .. 0, cot(z_0)
-  // Tiles are packed by their LIVE rows (4-row groups): a partner reads 16 rows of every tile (xw_readT), the rows past a
-  // tile's own are its successor's -- finite values that only reach accumulator rows which are never stored.  43 -> 16 KB
-  // per buffer at (20, 10, 8): 4 instead of 2 resident sweep blocks per CU (the third job of a sub-step queued for LDS).
-  static constexpr int HLAST = 4 * Dim<H, K>::HR(HT - 1);                   // rows of the last cot(out) tile
-  static constexpr int KROWS = 4 * Dim<H, K>::KSK;                          // rows of a K-tile
-  __device__ static constexpr int off(int t) {                             // first double of tile t
-    return XW_TSTRIDE * (t < HT ? 16 * t : 16 * (HT - 1) + HLAST + KROWS * (t - HT));
-  }
-  static constexpr int BUF = XW_TSTRIDE * (16 * (HT - 1) + HLAST + KROWS * M + 16);   // (+ 16 rows: reads past the last tile)
-  static_assert(BUF >= 3 * XW_TTILE, "the chain wave's epilogue borrows a buffer for its three transpose tiles");
-};
-#endif
-#ifndef XW_ODE_WIDE16
-template <int H, int K, int M, int OUTER, class SV>
-__device__ __forceinline__ void field_vjp(const FieldW<H, K>& w, const FieldWT<H, K>& wT, double t, const SV& sv,
-                                          const d4 (&yin)[Dim<H, K>::HT], const d4 (&ob)[Dim<H, K>::HT],
-                                          d4 (&yb)[Dim<H, K>::HT], d4& xpb, FieldG<H, K>& G, double* lds) {
-  typedef Dim<H, K> D;
-  constexpr bool PARAMS = OUTER == 1;
-  static_assert(D::HT <= 2, "two Q / R tile pairs in the LDS plan");
-  const double* rt1 = lds + 2 * XW_TTILE;
-  OuterOps o0;
-  double q1[4];
-  if (OUTER == 2) {
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht) {
-      if (ht == 0) xw_writeT_pn<D::HR(0)>(lds, ob[0]);
-      else xw_writeT_pn<D::HR(D::HT - 1)>(lds + DuoPlan<H, K, M>::off(ht), ob[ht]);
-    }
-  }
-  if (PARAMS) {
-    outer_post_ones<D::HR(0), K>(ob[0], sv.a, lds);
-    if (D::HT > 1) {
-      xw_writeT_n<D::HR(D::HT - 1)>(lds + 3 * XW_TTILE, ob[D::HT - 1]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-    outer_fetch(o0, lds, rt1);
-    if (D::HT > 1) outer_fetch1(q1, lds + 3 * XW_TTILE);
-  }
-  d4 ab = xw_zero4();
-#pragma unroll
-  for (int kb = 0; kb < D::HB; ++kb)
-#pragma unroll
-    for (int rb = 0; rb < D::KB; ++rb) ab[rb] = XW_MFMA4(wT.WoT[rb][kb], ob[kb >> 2][kb & 3], ab[rb]);
-  if (PARAMS) {
-    outer_fire(G.Wo[0], o0.a, o0.b);
-    if (D::HT > 1) outer_fire(G.Wo[D::HT - 1], q1, o0.b);
-  }
-  d4 zb = xw_zero4();
-#pragma unroll
-  for (int r = 0; r < D::KSK; ++r) zb[r] = ab[r] * (1.0 - sv.a[r] * sv.a[r]);
-#pragma unroll
-  for (int j = M - 2; j >= 0; --j) {
-    if constexpr (PARAMS) {
-      outer_post_ones<D::KSK, K>(zb, sv.z[j], lds);
-      outer_fetch(o0, lds, rt1);
-    }
-    if (OUTER == 2) xw_writeT_pn<D::KSK>(lds + DuoPlan<H, K, M>::off(D::HT + (M - 2 - j)), zb);
-    d4 tt = xw_zero4();
-#pragma unroll
-    for (int kb = 0; kb < D::KB; ++kb)
-#pragma unroll
-      for (int rb = 0; rb < D::KB; ++rb) tt[rb] = XW_MFMA4(wT.WhT[rb][kb], zb[kb], tt[rb]);
-    if (PARAMS) outer_fire(G.Wh, o0.a, o0.b);
-#pragma unroll
-    for (int r = 0; r < D::KSK; ++r) zb[r] = sv.gate(j, r, tt[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < D::KSK; ++r) xpb[r] += zb[r];
-  if (OUTER == 2) xw_writeT_pn<D::KSK>(lds + DuoPlan<H, K, M>::off(D::HT + M - 1), zb);
-  double rr[D::CT][4];
-  if (PARAMS) {
-    // one Q tile (the cotangent of z0) against the column tiles of [y ; t]: the time row makes column H collect the
-    // time-column gradient (row H & 15 of tile H >> 4: a tile of its own when H is a multiple of 16)
-    xw_writeT_n<D::KSK>(lds, zb);
-#pragma unroll
-    for (int ct = 0; ct < D::CT; ++ct) {
-      d4 yy = ct < D::HT ? yin[ct < D::HT ? ct : 0] : xw_zero4();
-      if (ct == (H >> 4)) set_row(yy, H & 15, t);
-      double* rt = lds + (ct == 0 ? 1 : 3 + ct) * XW_TTILE;            // tiles 1, 4, 5
-      if (ct == 0) xw_writeT_n<D::HR1(0)>(rt, yy);
-      else if (ct == 1) xw_writeT_n<D::HR1(1)>(rt, yy);
-      else xw_writeT_n<D::HR1(2)>(rt, yy);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    outer_fetch1(o0.a, lds);
-#pragma unroll
-    for (int ct = 0; ct < D::CT; ++ct) outer_fetch1(rr[ct], lds + (ct == 0 ? 1 : 3 + ct) * XW_TTILE);
-  }
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) yb[ht] = xw_zero4();
-#pragma unroll
-  for (int kb = 0; kb < D::KB; ++kb)
-#pragma unroll
-    for (int rb = 0; rb < D::HB; ++rb) yb[rb >> 2][rb & 3] = XW_MFMA4(wT.WyT[rb][kb], zb[kb], yb[rb >> 2][rb & 3]);
-  if (PARAMS) {
-#pragma unroll
-    for (int ct = 0; ct < D::CT; ++ct) outer_fire(G.Wy[ct], o0.a, rr[ct]);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-#else
-template <int H, int K, int M, int OUTER, class SV>
-__device__ __forceinline__ void field_vjp(const FieldW<H, K>& w, const FieldWT<H, K>& wT, double t, const SV& sv,
-                                          const d4 (&yin)[Dim<H, K>::HT], const d4 (&ob)[Dim<H, K>::HT],
-                                          d4 (&yb)[Dim<H, K>::HT], d4& xpb, FieldG<H, K>& G, double* lds) {
-  typedef Dim<H, K> D;
-  // OUTER: 0 = no weight gradients, 1 = this wave forms them itself (one LDS round trip per product, in the middle of the chain: the
-  // recomputing sweeps), 2 = duo sweep: this wave only posts its cotangent tiles (transposed) into `lds` = the evaluation's Q buffer
-  // (DuoPlan), the partner wave of the block (duo_outer) contracts them with the layer inputs it loads from the activation store
-  constexpr bool PARAMS = OUTER == 1;
-  constexpr bool POST = OUTER == 2;
-  typedef DuoPlan<H, K, M> P;
-  if (POST) {
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht) xw_writeT_n<4>(lds + P::off(ht), ob[ht]);
-  }
-  // cotangent of tanh(z_{m-1}): Wo^T cot(out), one chained accumulator over H / 4 k-steps
-  d4 ab = xw_zero4();
-#pragma unroll
-  for (int ks = 0; ks < D::KSH; ++ks) ab = XW_MFMA(wT.WoT[ks], ob[ks >> 2][ks & 3], ab);
-  if (PARAMS) {
-    // dWo[16 ht ..][:] += cot(out)[ht] (x) tanh(z_{m-1}) over the 16 paths (LDS transposes, 4 k-steps each); dWo.b elementwise
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht) {
-      outer_acc(G.Wo[ht], ob[ht], sv.a, lds);
-      G.bo[ht] = G.bo[ht] + ob[ht];
-    }
-  }
-  d4 zb;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) zb[r] = ab[r] * (1.0 - sv.a[r] * sv.a[r]);
-#pragma unroll
-  for (int j = M - 2; j >= 0; --j) {
-    if constexpr (PARAMS) {
-      outer_acc(G.Wh, zb, sv.z[j], lds);
-      G.bh = G.bh + zb;
-    }
-    if (POST) xw_writeT_n<4>(lds + P::off(D::HT + (M - 2 - j)), zb);      // cot(z_{j+1})
-    d4 tt = xw_zero4();
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) tt = XW_MFMA(wT.WhT[ks], zb[ks], tt);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) zb[r] = sv.gate(j, r, tt[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) xpb[r] += zb[r];
-  if (POST) xw_writeT_n<4>(lds + P::off(D::HT + M - 1), zb);              // cot(z_0)
-  if (PARAMS) {
-#pragma unroll
-    for (int ct = 0; ct < D::HT; ++ct) outer_acc(G.Wy[ct], zb, yin[ct], lds);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) G.wt[r] = fma(t, zb[r], G.wt[r]);
-  }
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-    yb[ht] = xw_zero4();
-#pragma unroll
-    for (int ks = 0; ks < D::KSK; ++ks) yb[ht] = XW_MFMA(wT.WyT[ht][ks], zb[ks], yb[ht]);
-  }
-}
-
-#endif
+// Form header, section 1: FieldW, FieldWT, load_field, load_field_T, field_fwd, FieldG, DuoPlan, field_vjp
+#define XW_ODE_SECTION 1
+#include XW_ODE_FORM
 // start scalar -> hidden state: initial_layers of src/model.py:78,97
 template <int H, int K>
 __device__ __forceinline__ void lift(const double* __restrict__ th, const UOff& o, double sv, d4 (&a0)[Dim<H, K>::HT],
@@ -1133,55 +740,9 @@ __device__ __forceinline__ void storeRowSums(double* dst, int rows, int r0, d4 q
   }
 }
 
-#ifndef XW_ODE_WIDE16
-// the field's weight-gradient accumulators -> one slab
-template <int H, int K, bool HID = true, bool IO = true>
-__device__ __forceinline__ void store_field_grads(double* slab, const UOff& o, int d, const FieldG<H, K>& G) {
-  typedef Dim<H, K> D;
-  if (HID) {
-    storeD(slab + o.Wh, K, K, K, 0, 0, G.Wh);
-    storeDcol(slab + o.Whb, 1, K, 0, K, G.Wh);
-  }
-  if (!IO) return;
-#pragma unroll
-  for (int ct = 0; ct < (H + 1 + 15) / 16; ++ct) {
-    storeD(slab + o.Win + d + 1, o.ldin, K, H, 0, 16 * ct, G.Wy[ct]);
-    if (ct == (H >> 4)) storeDcol(slab + o.Win + d, o.ldin, K, 0, H & 15, G.Wy[ct]);
-  }
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-    storeD(slab + o.Wo, K, H, K, 16 * ht, 0, G.Wo[ht]);
-    storeDcol(slab + o.Wob, 1, H, 16 * ht, K, G.Wo[ht]);
-  }
-}
-
-#else
-// the field's weight-gradient accumulators -> one slab (wide container: the biases and the time column are row sums over the 16 paths)
-template <int H, int K, bool HID = true, bool IO = true>
-__device__ __forceinline__ void store_field_grads(double* slab, const UOff& o, int d, const FieldG<H, K>& G) {
-  typedef Dim<H, K> D;
-  const int lane = xw_lane(), g = lane >> 4;
-  if (HID) {
-    storeD(slab + o.Wh, K, K, K, 0, 0, G.Wh);
-    storeRowSums(slab + o.Whb, K, 0, G.bh);
-  }
-  if (!IO) return;
-#pragma unroll
-  for (int ct = 0; ct < D::HT; ++ct) storeD(slab + o.Win + d + 1, o.ldin, K, H, 0, 16 * ct, G.Wy[ct]);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {                               // Win[:, d]: the time column
-    const double s_ = xw_sum_over_n(G.wt[r]);
-    const int row = g + 4 * r;
-    if ((lane & 15) == 0 && row < K) slab[o.Win + (long)row * o.ldin + d] = s_;
-  }
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-    storeD(slab + o.Wo, K, H, K, 16 * ht, 0, G.Wo[ht]);
-    storeRowSums(slab + o.Wob, H, 16 * ht, G.bo[ht]);
-  }
-}
-
-#endif
+// Form header, section 2: store_field_grads and the duo sweep's second wave, duo_outer (weight gradients of the field)
+#define XW_ODE_SECTION 2
+#include XW_ODE_FORM
 // what the reverse of one step l -> l+1 needs from the forward pass: the stage inputs and the stage activations
 template <int H, int K, int M, int S> struct Rec {
   d4 yi[S][Dim<H, K>::HT];
@@ -1459,11 +1020,6 @@ __device__ __forceinline__ void sweep_body(const BwdJobs& jobs, const double* __
   for (int ct = 0; ct < (H + 1 + 15) / 16; ++ct) G.Wy[ct] = xw_zero4();
 #pragma unroll
   for (int ht = 0; ht < D::HT; ++ht) G.Wo[ht] = xw_zero4();
-#ifdef XW_ODE_WIDE16
-  G.bh = G.wt = xw_zero4();
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) G.bo[ht] = xw_zero4();
-#endif
   d4 accFL[D::HT];
 #pragma unroll
   for (int ht = 0; ht < D::HT; ++ht) accFL[ht] = xw_zero4();
@@ -1741,363 +1297,6 @@ __device__ __forceinline__ void sweep_body(const BwdJobs& jobs, const double* __
                                 });
 }
 
-#ifndef XW_ODE_WIDE16
-// ---- the duo sweep's second wave: weight gradients of the field -------------------------------------------------------
-// For every field evaluation (same order as the chain wave, one evaluation behind it):
-//     dWo += cot(out) (x) [tanh(z_{m-1}) ; 1]     dWh += sum_j cot(z_{j+1}) (x) [relu(z_j) ; 1]     dWy += cot(z_0) (x) [y_in ; t]
-// contractions over the 16 paths of the tile, on v_mfma_f64_4x4x4_4b_f64 with the instruction's four blocks = the four
-// GROUPS OF FOUR PATHS:  acc[g][i][j] += sum_{k<4} q[4 rb + i][path 4 g + k] * r[4 cb + j][path 4 g + k].  One instruction
-// covers a 4 x 4 block of the gradient over ALL 16 paths (every block does useful work, 4-row / 4-column granularity: dWh
-// is 3 x 3 instructions per layer, 76 % of their multiply-adds useful, against 4 16x16x4 instructions at 43 %: 96 x 18
-// instead of 44 x 66 clocks per evaluation); the four per-group partial sums of an accumulator are added ONCE, at the end
-// of the sweep.  A operands: the cotangent tiles the chain wave posted (transposed) in LDS, lane (i, g, k) reads row
-// 4 rb + i, path 4 g + k.  B operands: the layer inputs straight from the activation store / the checkpoints in that same
-// lane layout, fetched a whole evaluation ahead (a register is reloaded for the next evaluation right behind the last
-// instruction that reads it).  Rows a block has no data for (the ones row that collects the bias gradient, zero padding)
-// read a constant table -- every lane loads, the loop stays ONE basic block (see duo_b_ptr).
-typedef const double __attribute__((address_space(1)))* xw_gptr;
-__device__ const double xw_duo_const[2][16] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
-                                               {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}};
-// where the operands of field evaluation e (chain-wave order: steps L-2 .. 0, stages S-1 .. 0) come from
-template <int H, int K, int M, int METHOD> struct DuoSrc {
-  const double* __restrict__ A;      // activation record of the step
-  const double* __restrict__ Yl;     // checkpoint y_l of the step (stage 0's input)
-  int i;                             // stage
-  double ti;                         // its time
-  __device__ __forceinline__ DuoSrc(const double* __restrict__ Y, const double* __restrict__ act,
-                                    const double* __restrict__ tf, int e, int L, int N, int tile) {
-    typedef RK<METHOD> T;
-    typedef ActLayout<H, K, M, T::S> AL;
-    const int l = L - 2 - e / T::S;
-    i = T::S - 1 - e % T::S;
-    A = act + ((long)l * ((N + 15) >> 4) + tile) * (AL::TOTAL * 16);
-    Yl = Y + (long)l * H * N;
-    const double t0 = tf[l];
-    ti = t0 + T::c(i) * (tf[l + 1] - t0);
-  }
-};
-template <int H, int K, int M> struct Duo4 {
-  static constexpr int KB1 = (K + 1 + 3) / 4;     // column blocks of [layer input ; 1]
-  static constexpr int HB1 = (H + 1 + 3) / 4;     // column blocks of [y ; t]
-  static constexpr int KB = Dim<H, K>::KB, HB = Dim<H, K>::HB;
-};
-// B operand of column block cb of a K-row activation tile [rows ; ones row ; zero padding]
-// (explicitly GLOBAL pointers: a select between a kernel argument and the address of a __device__ object is a generic
-//  pointer to the compiler, and flat loads return out of order -- every use would drain vmcnt(0))
-template <int H, int K, int M, int METHOD>
-__device__ __forceinline__ double duo_load_act(const DuoSrc<H, K, M, METHOD>& s, int jrow /* layer, M-1 = tanh */, int cb) {
-  typedef ActLayout<H, K, M, RK<METHOD>::S> AL;
-  const int lane = xw_lane(), j = lane & 3;
-  const int row = 4 * cb + j;
-  // lane j + 4 b + 16 k = (row 4 cb + j, path 4 k + b): lane-linear inside a full path-major block; a partial last block
-  // of p rows holds (row, path) at p * path + row
-  const int p = K - 4 * cb < 4 ? K - 4 * cb : 4;               // (compile-time after unrolling)
-  const int off = p == 4 ? lane : p * (lane >> 2) + j;
-  const xw_gptr src = row < K ? (xw_gptr)(s.A + (s.i * AL::STAGE + jrow * K + 4 * cb) * 16 + off) : (xw_gptr)&xw_duo_const[row == K ? 1 : 0][0];
-  return __builtin_nontemporal_load(src);
-}
-// ... of [y_in ; t ; zero padding]: rows of y_l (checkpoints, stage 0) or of the activation record (later stages);
-// branch-free (the loop must stay one basic block, or the compiler's wait-count bookkeeping falls back to vmcnt(0) at
-// its head); the time row is patched in where the block is USED (a select here would wait for the load)
-template <int H, int K, int M, int METHOD>
-__device__ __forceinline__ double duo_load_y(const DuoSrc<H, K, M, METHOD>& s, int cb, int N, int tile) {
-  typedef ActLayout<H, K, M, RK<METHOD>::S> AL;
-  static_assert(H % 4 == 0, "the stage inputs are whole path-major blocks");
-  const int lane = xw_lane(), j = lane & 3, b = (lane >> 2) & 3, k = lane >> 4;
-  const int row = 4 * cb + j;
-  const bool first = s.i == 0;                                // (wave-uniform)
-  // stage 0: the checkpoint y_l [H][N] (row-major); later stages: path-major blocks of the record, lane-linear
-  const long col = (long)tile * 16 + 4 * k + b;
-  const double* __restrict__ src_y = s.Yl + (long)row * N + (col < N - 1 ? col : N - 1);
-  const double* __restrict__ src_a = s.A + (long)(AL::YI + (s.i > 0 ? s.i - 1 : 0) * H + 4 * cb) * 16 + lane;
-  const xw_gptr src = row < H ? (xw_gptr)(first ? src_y : src_a) : (xw_gptr)&xw_duo_const[0][0];
-  return __builtin_nontemporal_load(src);
-}
-// A operand: rows 4 rb .. 4 rb + 3 of a transposed cotangent tile in LDS, posted by xw_writeT_pn (tile[row * XW_TSTRIDE +
-// 4 (path & 3) + (path >> 2)]): lane i + 4 b + 16 k = (row i, path 4 k + b) sits at position 4 b + k
-__device__ __forceinline__ double duo_readA(const double* tile, int rb) {
-  const int l = xw_lane();
-  return tile[(4 * rb + (l & 3)) * XW_TSTRIDE + ((l >> 2) & 3) * 4 + (l >> 4)];
-}
-// sum of an accumulator's four path-group partials (lane bits 2, 3), then element (row 4 rb + i, col 4 cb + j) from lane j + 16 i
-__device__ __forceinline__ double duo_fold(double x) {
-  x += __shfl_xor(x, 4);
-  x += __shfl_xor(x, 8);
-  return x;
-}
-template <int H, int K, int M, int METHOD>
-__device__ __forceinline__ void duo_outer(const BwdJobs& jobs, const double* __restrict__ tf, const double* __restrict__ th,
-                                          int L, int d, const double* qbuf, int vb) {
-  typedef Dim<H, K> D;
-  typedef RK<METHOD> T;
-  typedef DuoPlan<H, K, M> P;
-  typedef Duo4<H, K, M> Q;
-  typedef DuoSrc<H, K, M, METHOD> Src;
-  constexpr int NH = M > 1 ? M - 1 : 1;
-  xw_setprio(jobs.prio);          // (a lower priority for this wave than for the chain: no difference)
-  const int job = find_job(jobs, vb);
-  const double* __restrict__ Y = jobs.Y[job];
-  const double* __restrict__ act = jobs.act[job];
-  const int N = jobs.N[job];
-  const int tile = vb - jobs.tile0[job];
-  const int lane = xw_lane();
-  const UOff o = u_offsets(d, H, K);
-  double gWh[Q::KB][Q::KB1], gWo[Q::HB][Q::KB1], gWy[Q::KB][Q::HB1];
-#pragma unroll
-  for (int rb = 0; rb < Q::KB; ++rb) {
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) gWh[rb][cb] = 0.0;
-#pragma unroll
-    for (int cb = 0; cb < Q::HB1; ++cb) gWy[rb][cb] = 0.0;
-  }
-#pragma unroll
-  for (int rb = 0; rb < Q::HB; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) gWo[rb][cb] = 0.0;
-  double Ra[Q::KB1], Rr[NH][Q::KB1], Ry[Q::HB1];          // B operands of the evaluation in flight
-  const int E = (L - 1) * T::S;                            // field evaluations of the sweep
-  double ti_cur = 0.0;                                     // time of the evaluation whose operands are in R*
-  if (E > 0) {
-    const Src s0(Y, act, tf, 0, L, N, tile);
-    ti_cur = s0.ti;
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) Ra[cb] = duo_load_act<H, K, M, METHOD>(s0, M - 1, cb);
-#pragma unroll
-    for (int jj = M - 2; jj >= 0; --jj)
-#pragma unroll
-      for (int cb = 0; cb < Q::KB1; ++cb) Rr[jj][cb] = duo_load_act<H, K, M, METHOD>(s0, jj, cb);
-#pragma unroll
-    for (int cb = 0; cb < Q::HB1; ++cb) Ry[cb] = duo_load_y<H, K, M, METHOD>(s0, cb, N, tile);
-  }
-  const bool trow = (lane & 3) == (H & 3);                 // lanes of the time row inside its column block H >> 2
-  for (int e = 0; e < E; ++e) {
-    // the chain wave has posted evaluation e (and is free to start e + 1).  No fence: an acquire would drain vmcnt and
-    // with it the operand loads issued a whole evaluation ahead; LDS reads behind the barrier see the posted tiles.
-    asm volatile("s_barrier" ::: "memory");
-    const double* q = qbuf + (e & 1) * P::BUF;
-    const Src sn(Y, act, tf, e + 1 < E ? e + 1 : e, L, N, tile);   // (the last evaluation reloads its own operands: no branch)
-    // all A operands of the evaluation first (distinct registers, issued back to back: one exposed LDS latency per
-    // evaluation), then block by block the matrix instructions and right behind them the reloads for the next evaluation
-    double Ao[Q::HB], Az[M][Q::KB];
-#pragma unroll
-    for (int rb = 0; rb < Q::HB; ++rb) Ao[rb] = duo_readA(q + P::off(rb >> 2), rb & 3);
-#pragma unroll
-    for (int tq = 0; tq < M; ++tq)
-#pragma unroll
-      for (int rb = 0; rb < Q::KB; ++rb) Az[tq][rb] = duo_readA(q + P::off(D::HT + tq), rb);
-    __builtin_amdgcn_sched_barrier(0);
-    // cot(out) against [tanh ; 1]
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb)
-#pragma unroll
-      for (int rb = 0; rb < Q::HB; ++rb) gWo[rb][cb] = XW_MFMA4(Ao[rb], Ra[cb], gWo[rb][cb]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) Ra[cb] = duo_load_act<H, K, M, METHOD>(sn, M - 1, cb);
-    __builtin_amdgcn_sched_barrier(0);
-    // cot(z_{j+1}) against [relu(z_j) ; 1], j = M-2 .. 0 (tile order of the chain wave)
-#pragma unroll
-    for (int jj = M - 2; jj >= 0; --jj) {
-#pragma unroll
-      for (int cb = 0; cb < Q::KB1; ++cb)
-#pragma unroll
-        for (int rb = 0; rb < Q::KB; ++rb) gWh[rb][cb] = XW_MFMA4(Az[M - 2 - jj][rb], Rr[jj][cb], gWh[rb][cb]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int cb = 0; cb < Q::KB1; ++cb) Rr[jj][cb] = duo_load_act<H, K, M, METHOD>(sn, jj, cb);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // cot(z_0) against [y_in ; t]: column H of dWy (the time row) is the time-column gradient
-#pragma unroll
-    for (int cb = 0; cb < Q::HB1; ++cb) {
-      const double b = (cb == (H >> 2) && trow) ? ti_cur : Ry[cb];
-#pragma unroll
-      for (int rb = 0; rb < Q::KB; ++rb) gWy[rb][cb] = XW_MFMA4(Az[M - 1][rb], b, gWy[rb][cb]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int cb = 0; cb < Q::HB1; ++cb) Ry[cb] = duo_load_y<H, K, M, METHOD>(sn, cb, N, tile);
-    __builtin_amdgcn_sched_barrier(0);
-    ti_cur = sn.ti;
-  }
-  // ---- fold the path groups and store this tile's slab pieces: lane j + 16 i of block (rb, cb) holds (4 rb + i, 4 cb + j)
-  double* slab = jobs.gslab[job] + (long)tile * o.total;
-  const int i = lane >> 4, j = lane & 3;
-  const bool owner = ((lane >> 2) & 3) == 0;
-#pragma unroll
-  for (int rb = 0; rb < Q::KB; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) {
-      const double x = duo_fold(gWh[rb][cb]);
-      const int row = 4 * rb + i, col = 4 * cb + j;
-      if (owner && row < K) {
-        if (col < K) slab[o.Wh + row * K + col] = x;
-        else if (col == K) slab[o.Whb + row] = x;
-      }
-    }
-#pragma unroll
-  for (int rb = 0; rb < Q::HB; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < Q::KB1; ++cb) {
-      const double x = duo_fold(gWo[rb][cb]);
-      const int row = 4 * rb + i, col = 4 * cb + j;
-      if (owner && row < H) {
-        if (col < K) slab[o.Wo + row * K + col] = x;
-        else if (col == K) slab[o.Wob + row] = x;
-      }
-    }
-#pragma unroll
-  for (int rb = 0; rb < Q::KB; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < Q::HB1; ++cb) {
-      const double x = duo_fold(gWy[rb][cb]);
-      const int row = 4 * rb + i, col = 4 * cb + j;
-      if (owner && row < K) {
-        if (col < H) slab[o.Win + row * o.ldin + d + 1 + col] = x;
-        else if (col == H) slab[o.Win + row * o.ldin + d] = x;
-      }
-    }
-}
-
-#else    // XW_ODE_WIDE16
-// ---- the duo sweep's second wave in the wide container: weight gradients of the field on v_mfma_f64_16x16x4 --------------------
-// One wave that runs the adjoint chain AND its 15 outer products per evaluation paid an LDS round trip per product in the middle
-// of the chain and spilled 330 registers (641 us per sweep at the headline sample against 161 us without weight gradients).  As in
-// the narrow containers the chain wave only POSTS its cotangent tiles (field_vjp OUTER = 2: cot(out) x HT, cot(z_{j+1}) of every
-// tied layer, cot(z_0); two alternating buffers, one s_barrier per evaluation) and this wave, one evaluation behind, contracts
-// them over the 16 paths with the layer inputs it loads from the activation store / the checkpoints itself, a whole evaluation
-// ahead: 4 (HT + M - 1 + HT) matrix instructions per evaluation.  A operand = xw_readT of a posted tile (row i, path 4 ks + kk);
-// B operand = (row j, path 4 ks + kk) of a 16-row block of the record, whose 4-row blocks are path-major (act_store): double
-// 64 (j >> 2) + 4 (4 ks + kk) + (j & 3) of the block.  The bias gradients and the time column are row sums of the posted tiles: a
-// lane adds the A operands it reads anyway, the four lane groups are folded once at the end.
-template <int H, int K, int M, int METHOD>
-__device__ __forceinline__ void duo_outer(const BwdJobs& jobs, const double* __restrict__ tf, const double* __restrict__ th,
-                                          int L, int d, const double* qbuf, int vb) {
-  typedef Dim<H, K> D;
-  typedef RK<METHOD> T;
-  typedef DuoPlan<H, K, M> P;
-  typedef ActLayout<H, K, M, T::S> AL;
-  constexpr int NH = M > 1 ? M - 1 : 1;
-  xw_setprio(jobs.prio);
-  const int job = find_job(jobs, vb);
-  const double* __restrict__ Y = jobs.Y[job];
-  const double* __restrict__ act = jobs.act[job];
-  const int N = jobs.N[job];
-  const int tile = vb - jobs.tile0[job];
-  const int lane = xw_lane(), j = lane & 15, kk = lane >> 4;
-  const UOff o = u_offsets(d, H, K);
-  const int lo = 64 * (j >> 2) + 4 * kk + (j & 3);
-  const long ntile = (N + 15) >> 4;
-  long ycol[4];                                          // columns of the checkpoint this lane reads (clamped: the last tile's padding paths)
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const long c = (long)tile * 16 + 4 * ks + kk;
-    ycol[ks] = c < N ? c : N - 1;
-  }
-  d4 gWo[D::HT], gWy[D::HT], gWh = xw_zero4();
-  double sbo[D::HT], sbh = 0.0, swt = 0.0;
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) {
-    gWo[ht] = xw_zero4();
-    gWy[ht] = xw_zero4();
-    sbo[ht] = 0.0;
-  }
-  double Ra[4], Rr[NH][4], Ry[D::HT][4];                 // B operands of the evaluation in flight
-  const int E = (L - 1) * T::S;                          // field evaluations of the sweep (chain-wave order: steps L-2 .. 0, stages S-1 .. 0)
-  // operands of evaluation e: the record of its step, its stage, its time
-  auto load_eval = [&](int e, double& ti) {
-    const int l = L - 2 - e / T::S, i = T::S - 1 - e % T::S;
-    const double* __restrict__ A = act + ((long)l * ntile + tile) * (AL::TOTAL * 16) + lo;
-    const double t0 = tf[l];
-    ti = t0 + T::c(i) * (tf[l + 1] - t0);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) Ra[ks] = __builtin_nontemporal_load(A + (i * AL::STAGE + (M - 1) * K) * 16 + 16 * ks);
-#pragma unroll
-    for (int jj = 0; jj < M - 1; ++jj)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) Rr[jj][ks] = __builtin_nontemporal_load(A + (i * AL::STAGE + jj * K) * 16 + 16 * ks);
-    // the field's input: the checkpoint y_l [H][N] (stage 0) or the stage input kept in the record
-    const bool first = i == 0;                           // (wave-uniform)
-#pragma unroll
-    for (int ct = 0; ct < D::HT; ++ct)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const double* __restrict__ sy = Y + ((long)l * H + 16 * ct + j) * N + ycol[ks];
-        const double* __restrict__ sa = A + (long)(AL::YI + (i > 0 ? i - 1 : 0) * H + 16 * ct) * 16 + 16 * ks;
-        Ry[ct][ks] = __builtin_nontemporal_load(first ? sy : sa);
-      }
-  };
-  double ti_cur = 0.0;
-  if (E > 0) load_eval(0, ti_cur);
-  for (int e = 0; e < E; ++e) {
-    // the chain wave has posted evaluation e (and is free to start e + 1).  No fence: an acquire would drain vmcnt and with it the
-    // operand loads issued a whole evaluation ahead; LDS reads behind the barrier see the posted tiles.
-    asm volatile("s_barrier" ::: "memory");
-    const double* q = qbuf + (e & 1) * P::BUF;
-    double Ao[D::HT][4], Az[M][4];
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) Ao[ht][ks] = xw_readT(q + P::off(ht), ks);
-#pragma unroll
-    for (int tq = 0; tq < M; ++tq)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) Az[tq][ks] = xw_readT(q + P::off(D::HT + tq), ks);
-    __builtin_amdgcn_sched_barrier(0);
-    // cot(out) against tanh(z_{m-1})
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) gWo[ht] = XW_MFMA(Ao[ht][ks], Ra[ks], gWo[ht]);
-      sbo[ht] += (Ao[ht][0] + Ao[ht][1]) + (Ao[ht][2] + Ao[ht][3]);
-    }
-    // cot(z_{j+1}) against relu(z_j), j = M-2 .. 0 (tile order of the chain wave); the record keeps the layer INPUT z_j
-#pragma unroll
-    for (int jj = M - 2; jj >= 0; --jj) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const double r = Rr[jj][ks];
-        gWh = XW_MFMA(Az[M - 2 - jj][ks], r, gWh);
-      }
-      sbh += (Az[M - 2 - jj][0] + Az[M - 2 - jj][1]) + (Az[M - 2 - jj][2] + Az[M - 2 - jj][3]);
-    }
-    // cot(z_0) against the field's input; its row sums times t are the time column
-#pragma unroll
-    for (int ct = 0; ct < D::HT; ++ct)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) gWy[ct] = XW_MFMA(Az[M - 1][ks], Ry[ct][ks], gWy[ct]);
-    swt = fma(ti_cur, (Az[M - 1][0] + Az[M - 1][1]) + (Az[M - 1][2] + Az[M - 1][3]), swt);
-    __builtin_amdgcn_sched_barrier(0);
-    load_eval(e + 1 < E ? e + 1 : e, ti_cur);            // (the last evaluation reloads its own operands: no branch)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // ---- this tile's slab pieces: accumulator register r of lane (g, n) = element (row g + 4 r, column n)
-  double* slab = jobs.gslab[job] + (long)tile * o.total;
-  storeD(slab + o.Wh, K, K, K, 0, 0, gWh);                  // (u_layers = 1: zeros -- the slot of the missing tied layer)
-#pragma unroll
-  for (int ct = 0; ct < D::HT; ++ct) storeD(slab + o.Win + d + 1, o.ldin, K, H, 0, 16 * ct, gWy[ct]);
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) storeD(slab + o.Wo, K, H, K, 16 * ht, 0, gWo[ht]);
-  // row sums: lane (row j, group kk) holds its group's share
-  auto fold = [](double x) {
-    x += __shfl_xor(x, 16);
-    x += __shfl_xor(x, 32);
-    return x;
-  };
-  sbh = fold(sbh);
-  swt = fold(swt);
-#pragma unroll
-  for (int ht = 0; ht < D::HT; ++ht) sbo[ht] = fold(sbo[ht]);
-  if (kk == 0) {
-    if (j < K) slab[o.Whb + j] = sbh;
-    if (j < K) slab[o.Win + (long)j * o.ldin + d] = swt;
-#pragma unroll
-    for (int ht = 0; ht < D::HT; ++ht)
-      if (16 * ht + j < H) slab[o.Wob + 16 * ht + j] = sbo[ht];
-  }
-}
-
-#endif   // XW_ODE_WIDE16
 template <int H, int K, int M, int METHOD, bool PARAMS, bool SAVED, bool ADJ = false>
 __global__ void __launch_bounds__(64) k_ode_bwd(const BwdJobs jobs, const double* __restrict__ tf,
                                                 const double* __restrict__ th, int L, int d) {
@@ -2133,32 +1332,19 @@ __global__ void __launch_bounds__(XW_DUO_THREADS) k_ode_bwd_duo(const BwdJobs jo
   else duo_outer<H, K, M, METHOD>(jobs, tf, th, L, d, lds, vb);
 }
 
-#ifndef XW_ODE_WIDE16
-#include "xw_ode_n4.h"
-#endif   // (no narrow tiles in the wide container)
+// Form header, section 3: launch_fwd_narrow, launch_bwd (and the narrow-tile kernels of xw_ode_n4.h in the 4x4x4 form)
+#define XW_ODE_SECTION 3
+#include XW_ODE_FORM
 
 template <int H, int K, int M>
 int launch_fwd(int method, const FwdJobs& jobs, const double* t, const double* theta, int L, int d, hipStream_t s) {
   const dim3 grid(jobs.tile0[jobs.n]), block(64);
   bool act = true;                                     // all jobs or none, all in the same mode (checked by the caller)
   for (int i = 0; i < jobs.n; ++i) act = act && jobs.act[i] != nullptr;
-#ifndef XW_ODE_WIDE16
-  if (jobs.narrow) {
-    // narrow tiles (xw_ode_n4.h): the same grid of 16-path tiles, four waves of 4 paths each
-    switch (method * 3 + (act ? (jobs.x_only ? 2 : 1) : 0)) {
-      case 0: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 1: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 1>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 2: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 2>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 3: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 4: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 1>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 5: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 2>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      case 6: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 2, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-      default: return XW_E_ARG;
-    }
-    return xw_launch_status();
-  }
-#endif
-  switch (method * 3 + (act ? (jobs.x_only ? 2 : 1) : 0)) {
+  const int sel = method * 3 + (act ? (jobs.x_only ? 2 : 1) : 0);
+  int rc;
+  if (launch_fwd_narrow<H, K, M>(sel, jobs, t, theta, L, d, grid, s, rc)) return rc;
+  switch (sel) {
     case 0: hipLaunchKernelGGL((k_ode_fwd<H, K, M, 0, 0>), grid, block, 0, s, jobs, t, theta, L, d); break;
     case 1: hipLaunchKernelGGL((k_ode_fwd<H, K, M, 0, 1>), grid, block, 0, s, jobs, t, theta, L, d); break;
     case 2: hipLaunchKernelGGL((k_ode_fwd<H, K, M, 0, 2>), grid, block, 0, s, jobs, t, theta, L, d); break;
@@ -2169,67 +1355,6 @@ int launch_fwd(int method, const FwdJobs& jobs, const double* t, const double* t
     default: return XW_E_ARG;
   }
   return xw_launch_status();
-}
-template <int H, int K, int M, bool PARAMS>
-int launch_bwd(int method, const BwdJobs& jobs, const double* t, const double* theta, int L, int d, bool adj, bool narrow,
-               hipStream_t s) {
-  const dim3 grid(jobs.tile0[jobs.n]), block(64);
-#ifdef XW_ODE_WIDE16
-  // the wide container: no narrow tiles; the recomputing sweeps form their weight gradients themselves (OUTER = 1)
-  {
-    bool act_ = true;
-    for (int i = 0; i < jobs.n; ++i) act_ = act_ && jobs.act[i] != nullptr;
-    if (adj || !act_ || method > 1)
-      return XW_ODE_FN(xw_ode_bwd_recomp_w)(&jobs, t, theta, method, L, d, M, PARAMS ? 1 : 0, adj ? 1 : 0, (void*)s);
-    // from the activation store: without weight gradients one wave per tile, with them the duo sweep (chain wave + partner wave)
-    if (PARAMS) {
-      BwdJobs jd = jobs;
-      jd.spread = 0;
-      if (method == 0) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 0>), grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 1>), grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-    } else {
-      if (method == 0) hipLaunchKernelGGL((k_ode_bwd<H, K, M, 0, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 1, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-    }
-    return xw_launch_status();
-  }
-#else
-  if (narrow) {
-    // narrow tiles (xw_ode_n4.h): the same grid of 16-path tiles, four waves of 4 paths each; from the activation store only
-    if (adj || method > 1) return XW_E_ARG;
-    for (int i = 0; i < jobs.n; ++i)
-      if (jobs.act[i] == nullptr) return XW_E_ARG;
-    if (method == 0) hipLaunchKernelGGL((n4::k_ode_bwd_n4<H, K, M, 0, PARAMS>), grid, dim3(256), 0, s, jobs, t, theta, L, d);
-    else hipLaunchKernelGGL((n4::k_ode_bwd_n4<H, K, M, 1, PARAMS>), grid, dim3(256), 0, s, jobs, t, theta, L, d);
-    return xw_launch_status();
-  }
-  bool act = true;                                     // all jobs or none (checked by the caller)
-  for (int i = 0; i < jobs.n; ++i) act = act && jobs.act[i] != nullptr;
-  if (adj || !act || method > 1)      // (the recomputing sweeps live in an object of their own: XW_ODE_PART_RECOMP below)
-    return XW_ODE_FN(xw_ode_bwd_recomp_w)(&jobs, t, theta, method, L, d, M, PARAMS ? 1 : 0, adj ? 1 : 0, (void*)s);
-  // two rounds of tiles over the CUs: a spacer round in between (k_ode_bwd_duo)
-  static const int spread_on = [] { const char* e = getenv("XW_DUO_SPREAD"); return e ? atoi(e) : 1; }();
-  static const int ncu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
-  const int tiles = jobs.tile0[jobs.n];
-  BwdJobs jd = jobs;
-  // (exactly two rounds: 103 against 142 us at 512 tiles; with three rounds the third block of a CU meets the first again either
-  //  way -- 149 against 145 us --, and from four rounds on every SIMD hosts two waves whatever the order)
-  jd.spread = (spread_on && ncu > 0 && tiles > ncu && tiles <= 2 * ncu) ? ncu : 0;
-  const int rounds = jd.spread ? (tiles + ncu - 1) / ncu : 0;
-  const dim3 duo_grid(jd.spread ? (2 * (rounds - 1)) * ncu + (tiles - (rounds - 1) * ncu) : tiles);
-  switch (method) {
-    case 0:
-      if (PARAMS) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 0>), duo_grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 0, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-      break;
-    case 1:
-      if (PARAMS) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 1>), duo_grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 1, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-      break;
-    default: return XW_E_ARG;
-  }
-  return xw_launch_status();
-#endif
 }
 
 }  // namespace

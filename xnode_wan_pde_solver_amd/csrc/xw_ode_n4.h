@@ -1,4 +1,4 @@
-// xw_ode_n4.h -- NARROW-TILE stepper kernels: one wave = 4 Monte-Carlo paths x 16 rows (included by xw_ode.hip, inside its
+// xw_ode_n4.h -- NARROW-TILE stepper kernels: one wave = 4 Monte-Carlo paths x 16 rows (included by xw_ode_mfma4.h, inside xw_ode.hip's
 // anonymous namespace; same jobs, same activation store, same slabs, same results as the 16-path kernels).
 //
 // Why.  A 16-path tile is ONE instruction stream; N = 4096 paths are 256 of them for the chip's 1024 SIMDs, and a stream is
