@@ -81,7 +81,8 @@ def next_step(dt, ratio):
 
 
 def dopri5(f, y0, t, rtol=RTOL, atol=ATOL, count=None, frozen=None, max_steps=10000):
-    """-> (ys [N, L, ...] stacked along dim 1 like odeint_fixed, info dict(steps [(t0, dt)], n_att, n_acc, gap = min |ratio - 1|))
+    """-> (ys [N, L, ...] stacked along dim 1 like odeint_fixed, info dict(steps [(t0, dt)], n_att, n_acc, gap = min |ratio - 1|,
+    cond = per attempt (condition number of the error ratio, whether the next step size moves with it)))
     t: float64 [L], increasing.  Autograd flows through the controller unless `frozen` is given."""
     t = t.to(F64)
     L = t.shape[0]
@@ -91,7 +92,7 @@ def dopri5(f, y0, t, rtol=RTOL, atol=ATOL, count=None, frozen=None, max_steps=10
     while i < L and not bool(t[i] > t[0]):
         out[i] = y0
         i += 1
-    steps, n_att, gap = [], 0, math.inf
+    steps, n_att, gap, cond = [], 0, math.inf, []
     t0, y = t[0], y0
     if frozen is None:
         dt = initial_step(f, t0, y0, f0, rtol, atol, count)
@@ -109,6 +110,14 @@ def dopri5(f, y0, t, rtol=RTOL, atol=ATOL, count=None, frozen=None, max_steps=10
             gap = min(gap, abs(float(ratio.detach()) - 1.0))
             accept = bool(ratio <= 1)
             dt_next = next_step(dt, ratio)
+            # the condition number of this attempt's ratio: the error estimate is a sum of seven terms that nearly cancel (the
+            # weights E add up to zero), so one unit of relative rounding in the terms moves the ratio by `cond` units -- and,
+            # where the step-size factor is not clamped, the next step size by cond / 5
+            with torch.no_grad():
+                mag = rms(sum(k[q].abs() * abs(float(dt) * E[q]) for q in range(7)) / tol, count)
+                fac = float(dt_next / dt)
+                free = float(ratio) > 0 and (1.0 if ratio < 1 else DFACTOR) < fac < IFACTOR
+                cond.append((float(mag / ratio) if float(ratio) > 0 else math.inf, free))
         else:
             accept, dt_next = True, None
         if accept:
@@ -124,7 +133,7 @@ def dopri5(f, y0, t, rtol=RTOL, atol=ATOL, count=None, frozen=None, max_steps=10
             t0, y, f0 = t1, y1, f1
         if frozen is None:
             dt = dt_next
-    return torch.stack(out, 1), dict(steps=steps, n_att=n_att, n_acc=len(steps), gap=gap)
+    return torch.stack(out, 1), dict(steps=steps, n_att=n_att, n_acc=len(steps), gap=gap, cond=cond)
 
 
 def u_net(theta, config, X, start_value, rtol=RTOL, atol=ATOL, frozen=None):
