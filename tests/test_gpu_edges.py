@@ -27,6 +27,9 @@ Regions pinned as untouched (from the code):
                                   slots of their own, csrc/xw_ode.hip act_store).  At (64, 16) every double row of the store is
                                   checked as written; at (20, 10) the partial 4-row block (K mod 4 = 2) leaves slots unused inside the
                                   record, so the narrow-tile cases check its guards only
+                                  (this file's cases.  tests/test_gpu_stepper_inventory.py pins more, from act_store: the 16-path
+                                  forward's full store has every double row written in all three containers, its x-only store the tanh
+                                  rows written and the other double rows untouched; the narrow-tile forward's store stays guard-checked)
 
 Tolerances at the widest / deepest corners: ORACLE_SPREAD below holds the float64 oracle's own rounding spread, measured on the CPU
 (oracle_spread(): the case as written against the same case with hidden units permuted and the path order reversed --
@@ -677,6 +680,25 @@ def _permuted(theta, d, H, K, seed):
     return {k: v.contiguous() for k, v in tp.items()}, ph, pk
 
 
+def _unpermuted(k, v, d, inv_h, inv_k):
+    """parameter k's gradient v of a network permuted by _permuted, back in the original order of the hidden units"""
+    if k in ('IL0_w', 'IL0_b', 'IL2_b', 'IL4_b', 'Wo_b'):
+        return v[inv_h]
+    if k in ('IL2_w', 'IL4_w'):
+        return v[inv_h][:, inv_h]
+    if k == 'Win':
+        return v[inv_k][:, torch.cat((torch.arange(d + 1), d + 1 + inv_h))]
+    if k in ('Win_b', 'Wh_b'):
+        return v[inv_k]
+    if k == 'Wh':
+        return v[inv_k][:, inv_k]
+    if k == 'Wo':
+        return v[inv_h][:, inv_k]
+    if k == 'FL_w':
+        return v[:, inv_h]
+    return v
+
+
 def dopri5_grid_spread(d, H, K, N, L, seed):
     """the restatement's own spread of the accepted grid for one dopri5 fixture (GRID_TOL's metric): as written against hidden units
     permuted and paths reversed; None if the two runs do not take the same attempts"""
@@ -707,29 +729,12 @@ def oracle_spread(c):
     g2 = _grads(u2, leaves2, cot[rev].contiguous())
     inv_h, inv_k = torch.argsort(ph), torch.argsort(pk)
 
-    def back(k, v):                                 # a gradient of the permuted network in the original order
-        if k in ('IL0_w', 'IL0_b', 'IL2_b', 'IL4_b', 'Wo_b'):
-            return v[inv_h]
-        if k in ('IL2_w', 'IL4_w'):
-            return v[inv_h][:, inv_h]
-        if k == 'Win':
-            return v[inv_k][:, torch.cat((torch.arange(d + 1), d + 1 + inv_h))]
-        if k in ('Win_b', 'Wh_b'):
-            return v[inv_k]
-        if k == 'Wh':
-            return v[inv_k][:, inv_k]
-        if k == 'Wo':
-            return v[inv_h][:, inv_k]
-        if k == 'FL_w':
-            return v[:, inv_h]
-        return v
-
     def rel(a, b):
         return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-300)
 
     sv = max(rel(u2.detach()[rev], u.detach()), rel(Y2[:, inv_h][:, :, rev], Y))
-    pairs = [(g2[0][rev], g[0]), (g2[1][rev], g[1])] + [(back(k, a), b) for k, a, b in zip(U_ORDER, g2[2:], g[2:])]
-    pairs.append((torch.cat([back(k, a).reshape(-1) for k, a in zip(U_ORDER, g2[2:])]), torch.cat([b.reshape(-1) for b in g[2:]])))
+    pairs = [(g2[0][rev], g[0]), (g2[1][rev], g[1])] + [(_unpermuted(k, a, d, inv_h, inv_k), b) for k, a, b in zip(U_ORDER, g2[2:], g[2:])]
+    pairs.append((torch.cat([_unpermuted(k, a, d, inv_h, inv_k).reshape(-1) for k, a in zip(U_ORDER, g2[2:])]), torch.cat([b.reshape(-1) for b in g[2:]])))
     return sv, max(rel(a, b) for a, b in pairs)
 
 
