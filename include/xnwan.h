@@ -114,6 +114,15 @@ typedef struct { const double* xT; const double* start; const double* Y; const d
                   *   w = res_w[n] or res_w[l][n] (res_w_per_point), d(c u)/du = res_c + u res_cp (tabulated c, dc/du) or
                   *   res_kappa2 u (c = kappa u, res_c == NULL): sweep B starts right behind the test network. */
                  int res_w_per_point; const double* res_w; const double* res_c; const double* res_cp; double res_kappa2;
+                 /* res_first_only == 3: the MERGED cotangent of a generator sub-step on one GPU, where the global I is known
+                  * before the sweep starts --
+                  *   ubar[l][n] = [kind 1 with (res_baseA, res_coefA, res_refA)] + s [kind 2 with the fields above],
+                  *   s = 2 / res_scal[0]  (res_scal: DEVICE pointer to the sub-step's sums, I = scal[0]; read once per wave in
+                  *   front of the time loop).  By linearity J^T A + (2/I) J^T B = J^T (A + (2/I) B): one interior sweep with
+                  *   weight gradients where kinds 1 and 2 take two, and xw_adam then sums ONE slab set with coefB = 1.
+                  *   Needs res_u, res_ref (= v), res_w, res_refA (the initial penalty's reference, h) and res_scal: XW_E_ARG
+                  *   otherwise.  Every stepper family takes it. */
+                 const double* res_scal; const double* res_refA; double res_coefA; double res_baseA;
                } XwOdeBwdJob;
 int xw_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
                      int method, int L, int d, int H, int K, int m, int mode, void* stream);
@@ -383,7 +392,8 @@ typedef struct {
   int w_per_point, amode, pair_i, pair_b;
   int ns_u, ns_b;                 /* slabs of the interior / boundary sweeps (xw_ode_bwd_slabs) */
   int narrow;                     /* narrow-tile launches: bit 0 forward (generator), 1 boundary forward alone, 2 the sweeps launch of the
-                                     generator sub-step (A, boundary on the same grid, B: one launch), 3 boundary sweep alone, 4 unused,
+                                     generator sub-step (A, boundary on the same grid, B: one launch), 3 boundary sweep alone, 4 the merged form's sweeps launch
+                                     (interior kind 3 + boundary),
                                      5 x-only sweep (generator, unfused), 6 forward (discriminator), 7 x-only sweep (discriminator) */
   int sharded;                    /* != 0: N / Nb are this rank's SHARE of a group of Nglob / Nbglob paths (either may be 0); the
                                      sub-step runs XwSolverState.exchange between its launches */
@@ -408,6 +418,11 @@ typedef struct {
   XwExchangeFn exchange;
   void* exchange_ctx;
   double* pack_u;
+  /* != 0: xw_substep_gen takes the merged form (XwOdeBwdJob.res_first_only == 3) for the groups it applies to -- one process,
+   * no carried gradient, pollution == 1 without the continuous adjoint, boundary paths on the interior's grid, no pairwise
+   * sums, a = identity and b = 0: forward pass -> x-only sweep beside the test network, then reduction, ONE sweep launch
+   * (interior kind 3 + boundary) and the update.  Every other group runs the three-job form whatever this says. */
+  int merged_sweep;
 } XwSolverState;
 /* skip_v: v, dv/dt, nabla_x v(t_0) of this group are still those of the current phi and sample (opt-in reuse);
  * store_record: the test network's forward also stores its layer inputs (vact) for xw_disc_bwd;

@@ -25,7 +25,8 @@ class XwOdeBwdJob(ctypes.Structure):
     _fields_ = [('xT', c_vp), ('start', c_vp), ('Y', c_vp), ('act', c_vp), ('ubar', c_vp), ('gx', c_vp), ('gs', c_vp),
                 ('gslab', c_vp), ('N', c_int), ('res_first_only', c_int), ('res_u', c_vp), ('res_ref', c_vp),
                 ('res_coef', ctypes.c_double), ('res_base', ctypes.c_double), ('res_w_per_point', c_int), ('res_w', c_vp),
-                ('res_c', c_vp), ('res_cp', c_vp), ('res_kappa2', ctypes.c_double)]
+                ('res_c', c_vp), ('res_cp', c_vp), ('res_kappa2', ctypes.c_double), ('res_scal', c_vp), ('res_refA', c_vp),
+                ('res_coefA', ctypes.c_double), ('res_baseA', ctypes.c_double)]
 
 
 class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
@@ -52,7 +53,8 @@ class XwSolverState(ctypes.Structure):
                                       'lag_hi')]
                 + [(n, c_dbl) for n in ('alpha', 'pollution', 'lr_u', 'lr_v', 'beta1', 'beta2', 'eps')]
                 + [(n, c_vp) for n in ('theta', 'phi', 'scal', 'grad_u', 'grad_v', 'm_u', 'v_u', 'm_v', 'v_v', 'step_u', 'step_v',
-                                       'lag_u', 'exchange', 'exchange_ctx', 'pack_u')])
+                                       'lag_u', 'exchange', 'exchange_ctx', 'pack_u')]
+                + [('merged_sweep', c_int)])
 
 
 # XwSolverState.exchange: int (*)(double* buf, int count, void* ctx, void* stream) -- xw_allreduce's own signature

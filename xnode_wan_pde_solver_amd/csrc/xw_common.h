@@ -82,6 +82,20 @@ __device__ __forceinline__ void xw_st_g(double v, double* p) { *(xw_gp)p = v; }
 __device__ __forceinline__ double xw_ld_nt(const double* p) { return __builtin_nontemporal_load((xw_gcp)p); }
 __device__ __forceinline__ void xw_st_nt(double v, double* p) { __builtin_nontemporal_store(v, (xw_gp)p); }
 
+// ---- the two residual cotangents of a generator sub-step's interior sweeps (XwOdeBwdJob.res_first_only) ------------------
+// One definition for every stepper family: kind 1 is xw_cot_init alone, kind 2 xw_cot_weak alone, kind 3 (the merged
+// sweep) xw_cot_merged = init + s weak with s = 2 / I.
+//   init: base + coef (u - ref) at the first time index, base elsewhere          (pollution + the initial-value penalty)
+//   weak: coef d(c u)/du v w (+ base v at the last time index)                   (dI/du of the weak form)
+__device__ __forceinline__ double xw_cot_init(double base, double coef, double u, double ref, bool first) {
+  return first ? fma(coef, u - ref, base) : base;
+}
+__device__ __forceinline__ double xw_cot_weak(double coef, double base, double dcu, double v, double w, bool last) {
+  const double g = coef * dcu * v * w;
+  return last ? fma(base, v, g) : g;
+}
+__device__ __forceinline__ double xw_cot_merged(double a, double s, double b) { return fma(s, b, a); }
+
 // ---- lane helpers -------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int xw_lane() { return threadIdx.x & 63; }
 

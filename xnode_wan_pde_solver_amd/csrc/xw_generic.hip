@@ -437,7 +437,7 @@ int xwg_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const
   for (int i = 0; i < njobs; ++i) {
     const XwOdeBwdJob& j = jobs[i];
     if (!j.xT || !j.start || !j.Y || j.N < 1) return XW_E_ARG;
-    if (j.res_u != nullptr && j.ubar != nullptr) return XW_E_ARG;
+    if (!cot_job_ok(j)) return XW_E_ARG;
     if ((mode & 2) && !j.gslab) return XW_E_ARG;
     if ((mode & 1) && !(mode & 4) && (!j.gx || !j.gs)) return XW_E_ARG;
     if (mode & 2) {

@@ -356,12 +356,16 @@ struct BwdJobs {
   const double* res_u[XW_MAXJOBS];
   const double* res_ref[XW_MAXJOBS];
   double res_coef[XW_MAXJOBS], res_base[XW_MAXJOBS];
-  int res_first[XW_MAXJOBS];        // XwOdeBwdJob.res_first_only: 0 / 1 residual forms, 2 = the weak form's dI/du
+  int res_first[XW_MAXJOBS];        // XwOdeBwdJob.res_first_only: 0 / 1 residual forms, 2 = the weak form's dI/du, 3 = merged (1 + s * 2)
   const double* res_w[XW_MAXJOBS];
   const double* res_c[XW_MAXJOBS];
   const double* res_cp[XW_MAXJOBS];
   double res_kappa2[XW_MAXJOBS];
   int res_wpp[XW_MAXJOBS];
+  // kind 3 (merged): kind 1 with these fields + (2 / res_scal[0]) kind 2 with the ones above
+  const double* res_scal[XW_MAXJOBS];
+  const double* res_refA[XW_MAXJOBS];
+  double res_coefA[XW_MAXJOBS], res_baseA[XW_MAXJOBS];
 };
 // cotangent of u at (time index l, path col) of job `job`: a stored array, all ones, or formed from a residual on the fly
 // (the initial-value and the boundary penalty: no cotangent kernel between the forward pass and these sweeps)
@@ -369,22 +373,21 @@ __device__ __forceinline__ double cot_u(const BwdJobs& jobs, int job, const doub
                                         int L) {
   const double* __restrict__ ru = jobs.res_u[job];
   if (ru != nullptr) {
-    if (jobs.res_first[job] == 2) {
+    if (jobs.res_first[job] >= 2) {
       // dI/du of the weak form (xw_gen_cotangents' basis B, src/loss.py:64,70): coef d(c(u) u)/du v w, + base v at t_{L-1}
       const long p = (long)l * N + col;
       const double ul = ru[p], vl = jobs.res_ref[job][p];
       const double wl = jobs.res_wpp[job] ? jobs.res_w[job][p] : jobs.res_w[job][col];
       const double dcu = jobs.res_c[job] != nullptr ? jobs.res_c[job][p] + ul * jobs.res_cp[job][p] : jobs.res_kappa2[job] * ul;
-      double gB = jobs.res_coef[job] * dcu * vl * wl;
-      if (l == L - 1) gB += jobs.res_base[job] * vl;
-      return gB;
+      const double gB = xw_cot_weak(jobs.res_coef[job], jobs.res_base[job], dcu, vl, wl, l == L - 1);
+      if (jobs.res_first[job] == 2) return gB;
+      // merged (xw_gen_cotangents with scal): pollution + the initial penalty at t_0, + (2 / I) dI/du
+      return xw_cot_merged(xw_cot_init(jobs.res_baseA[job], jobs.res_coefA[job], ul, jobs.res_refA[job][col], l == 0),
+                           2.0 / jobs.res_scal[job][0], gB);
     }
+    if (jobs.res_first[job]) return xw_cot_init(jobs.res_base[job], jobs.res_coef[job], ru[col], jobs.res_ref[job][col], l == 0);
     double r = jobs.res_base[job];
-    if (jobs.res_first[job]) {
-      if (l == 0) r += jobs.res_coef[job] * (ru[col] - jobs.res_ref[job][col]);
-    } else {
-      r += jobs.res_coef[job] * (ru[(long)l * N + col] - jobs.res_ref[job][(long)l * N + col]);
-    }
+    r += jobs.res_coef[job] * (ru[(long)l * N + col] - jobs.res_ref[job][(long)l * N + col]);
     return r;
   }
   return ubar != nullptr ? ubar[(long)l * N + col] : 1.0;
@@ -393,23 +396,34 @@ __device__ __forceinline__ double cot_u(const BwdJobs& jobs, int job, const doub
 // cot_u() above branches on the kind of cotangent, and a value loaded inside a branch is used inside it: the
 // wait in front of that use is vmcnt(0) -- it would drain the stage records this wave has just requested for the NEXT stage,
 // i.e. expose a full memory latency in every step of a chain that is only ~2 - 4 k clocks long.  Here every kind is the same
-// straight-line code: up to five loads from lane pointers prepared once (a pointer that a kind does not need aims at res_u /
+// straight-line code: up to six loads from lane pointers prepared once (a pointer that a kind does not need aims at res_u /
 // Y, finite data; its value is dropped by a select, never multiplied in), issued a whole step before their use.
 //   affine kinds:  ub = cb + [st] + coef (ru - rf) [only at l = 0 when `first`]        (ones / stored / residual forms)
 //   weak kind   :  ub = coef d(c u)/du v w  (+ base v at l = L - 1),  d(c u)/du = c + u c' (tabulated) or kappa2 u
+//   merged kind :  ub = [baseA + coefA (u - h) at l = 0] + s (weak kind),  s = 2 / I read ONCE here, in front of the time
+//                  loop; a sixth load (h, stride 0) rides in the weak kind's request, dropped by a select when not merged
 struct Cot4 {
-  const double *p0, *p1, *p2, *p3, *p4;      // st | ru, rf | (weak) u, v, w, c, c'      lane pointers at time index 0
+  const double *p0, *p1, *p2, *p3, *p4, *p5; // st | ru, rf | (weak) u, v, w, c, c', h   lane pointers at time index 0
   long s0, s1, s2;                           // strides (doubles) per time index of p0, (p1, p2 | p3, p4), p2 of the weak kind
-  double cb, coef, base, kappa2;
-  bool weak, use_st, use_res, first, tab, valid;
+  double cb, coef, base, kappa2, s, coefA, baseA;
+  bool weak, use_st, use_res, first, tab, valid, merged;
 };
-struct CotRaw { double a, b, c, d, e; };
+struct CotRaw { double a, b, c, d, e, f; };
 __device__ __forceinline__ Cot4 make_cot(const BwdJobs& jobs, int job, int N, int col, bool valid, const double* dummy) {
   Cot4 c;
   const double* ru = jobs.res_u[job];
   const double* ubar = jobs.ubar[job];
   c.valid = valid;
-  c.weak = ru != nullptr && jobs.res_first[job] == 2;
+  c.weak = ru != nullptr && jobs.res_first[job] >= 2;
+  c.merged = ru != nullptr && jobs.res_first[job] == 3;
+  c.coefA = jobs.res_coefA[job];
+  c.baseA = jobs.res_baseA[job];
+  // One load and one FP64 divide per wave, in front of the time loop, for EVERY kind (no branch around a load): the kinds that
+  // are not merged read Y[0] and drop the quotient by a select.  The weak kinds (2, 3) also carry the sixth load per step, h for
+  // kind 3, Y[col] (stride 0, a cache hit after the first step) for kind 2.  What that costs the sweeps that gained nothing --
+  // x-only, boundary, kind 2 alone -- has not been measured; tools/kernel_times.py prints those launches.
+  c.s = 2.0 / xw_ld_g(c.merged ? jobs.res_scal[job] : dummy);       // (not merged: finite or not, dropped by the select)
+  c.p5 = (c.merged ? jobs.res_refA[job] : dummy) + col;
   c.use_res = ru != nullptr && !c.weak;
   c.use_st = ru == nullptr && ubar != nullptr;
   c.first = c.use_res && jobs.res_first[job] != 0;
@@ -438,9 +452,10 @@ template <bool WEAK> __device__ __forceinline__ CotRaw cot_issue(const Cot4& c, 
     r.c = xw_ld_g(c.p2 + l * c.s2);
     r.d = xw_ld_g(c.p3 + l * c.s1);
     r.e = xw_ld_g(c.p4 + l * c.s1);
+    r.f = xw_ld_g(c.p5);
   } else {
     r.c = xw_ld_g(c.p2 + l * c.s1);
-    r.d = r.e = 0.0;
+    r.d = r.e = r.f = 0.0;
   }
   return r;
 }
@@ -448,12 +463,14 @@ template <bool WEAK> __device__ __forceinline__ double cot_value(const Cot4& c, 
   double ub;
   if (WEAK) {
     const double dcu = c.tab ? fma(r.a, r.e, r.d) : c.kappa2 * r.a;        // (as cot_u: c + u c', or kappa2 u)
-    ub = c.coef * dcu * r.b * r.c;
-    if (l == L - 1) ub = fma(c.base, r.b, ub);
+    ub = xw_cot_weak(c.coef, c.base, dcu, r.b, r.c, l == L - 1);
+    if (c.merged) ub = xw_cot_merged(xw_cot_init(c.baseA, c.coefA, r.a, r.f, l == 0), c.s, ub);
+  } else if (c.first) {
+    ub = xw_cot_init(c.cb, c.coef, r.b, r.c, l == 0);
   } else {
     ub = c.cb;
     if (c.use_st) ub += r.a;
-    if (c.use_res && (!c.first || l == 0)) ub = fma(c.coef, r.b - r.c, ub);
+    if (c.use_res) ub = fma(c.coef, r.b - r.c, ub);
   }
   return c.valid ? ub : 0.0;
 }
@@ -1423,9 +1440,14 @@ extern "C" int XW_ODE_FN(xw_ode_bwd_multi_w)(const XwOdeBwdJob* jobs, int njobs,
     J.res_cp[i] = on ? jobs[i].res_cp : nullptr;
     J.res_kappa2[i] = on ? jobs[i].res_kappa2 : 0.0;
     J.res_wpp[i] = on ? jobs[i].res_w_per_point : 0;
+    J.res_scal[i] = on ? jobs[i].res_scal : nullptr;
+    J.res_refA[i] = on ? jobs[i].res_refA : nullptr;
+    J.res_coefA[i] = on ? jobs[i].res_coefA : 0.0;
+    J.res_baseA[i] = on ? jobs[i].res_baseA : 0.0;
     if (on && jobs[i].res_u && (!jobs[i].res_ref || jobs[i].ubar)) return XW_E_ARG;
-    if (on && jobs[i].res_u && jobs[i].res_first_only == 2 && (!jobs[i].res_w || (!jobs[i].res_c != !jobs[i].res_cp))) return XW_E_ARG;
-    if (on && (jobs[i].res_first_only < 0 || jobs[i].res_first_only > 2)) return XW_E_ARG;
+    if (on && jobs[i].res_u && jobs[i].res_first_only >= 2 && (!jobs[i].res_w || (!jobs[i].res_c != !jobs[i].res_cp))) return XW_E_ARG;
+    if (on && (jobs[i].res_first_only < 0 || jobs[i].res_first_only > 3)) return XW_E_ARG;
+    if (on && jobs[i].res_first_only == 3 && (!jobs[i].res_u || !jobs[i].res_scal || !jobs[i].res_refA)) return XW_E_ARG;
     J.gx[i] = (on && (mode & 1)) ? jobs[i].gx : nullptr;
     J.gs[i] = (on && (mode & 1)) ? jobs[i].gs : nullptr;
     J.gslab[i] = (on && (mode & 2)) ? jobs[i].gslab : nullptr;

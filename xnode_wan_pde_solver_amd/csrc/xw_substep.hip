@@ -86,6 +86,47 @@ extern "C" int xw_substep_gen(const XwGroup* g, const XwSolverState* s, int skip
   const bool joint = have_i && have_b && g->same_grid;
   const int adj = s->adjoint ? 8 : 0;
   void* const main_stream = stream;
+  // The merged form (XwOdeBwdJob.res_first_only == 3): with the global I on the device before the parameter sweep starts, the
+  // interior sweeps A and B are ONE sweep over A + (2/I) B.  nabla_x u(t_0), which I needs, comes from an x-only sweep (one wave
+  // per tile, no weight gradients) that runs on the side chain beside the test network, as in the discriminator sub-step.
+  const bool merged = s->merged_sweep && !shard && accum == nullptr && fused_x && joint && !g->pair_i && !g->pair_b && g->A0 == nullptr &&
+                      g->B0 == nullptr;
+  if (merged) {
+    Side* sd = side_of_current_device();
+    if (sd == nullptr) return XW_E_ARG;
+    XW_HIP(hipEventRecord(sd->fork, (hipStream_t)main_stream));
+    XW_HIP(hipStreamWaitEvent(sd->s, sd->fork, 0));
+    if (!skip_v) XW_TRY(test_net(g, s, s->v_blocks, store_record ? g->vact : nullptr, main_stream));
+    {
+      XwOdeFwdJob jobs[2] = {fwd_job(g->xT, g->start, g->u, g->Y, g->act, g->N, 0, (g->narrow >> 0) & 1),
+                             fwd_job(g->xbT, g->start_b, g->ub, g->Yb, g->act_b, g->Nb, 0, (g->narrow >> 0) & 1)};
+      XW_TRY(xw_ode_fwd_multi(jobs, 2, g->t, s->theta, s->method, g->L, g->d, s->H, s->K, s->m, s->scal, (void*)sd->s));
+      XwOdeBwdJob jx = bwd_job(g->xT, g->start, g->Y, g->act, g->N);
+      jx.gx = g->gx; jx.gs = g->gs;
+      XW_TRY(xw_ode_bwd_multi(&jx, 1, g->t, s->theta, s->method, g->L, g->d, s->H, s->K, s->m, 1 | (((g->narrow >> 5) & 1) ? 16 : 0),
+                              (void*)sd->s));
+    }
+    XW_HIP(hipEventRecord(sd->fwd, sd->s));
+    XW_HIP(hipStreamWaitEvent((hipStream_t)main_stream, sd->fwd, 0));
+    XW_TRY(contract(g, s, s->step_u, true, true, main_stream));          // -> I = scal[0], the loss values, the step counter
+    XwOdeBwdJob jobs[2];
+    jobs[0] = bwd_job(g->xT, g->start, g->Y, g->act, g->N);
+    jobs[0].gslab = g->slabA;
+    jobs[0].res_first_only = 3; jobs[0].res_u = g->u; jobs[0].res_ref = g->v;
+    jobs[0].res_coef = g->Vol / g->Nglob / g->L * g->s3_scale; jobs[0].res_base = g->Vol / g->Nglob;
+    jobs[0].res_w_per_point = g->w_per_point; jobs[0].res_w = g->w; jobs[0].res_c = g->c; jobs[0].res_cp = g->cp;
+    jobs[0].res_kappa2 = 2.0 * g->ckappa;
+    jobs[0].res_scal = s->scal; jobs[0].res_refA = g->h; jobs[0].res_coefA = 2.0 * s->alpha / g->Nglob; jobs[0].res_baseA = s->pollution;
+    jobs[1] = bwd_job(g->xbT, g->start_b, g->Yb, g->act_b, g->Nb);
+    jobs[1].gslab = g->slabA + (long)g->ns_u * s->Pu;
+    jobs[1].res_u = g->ub; jobs[1].res_ref = g->g; jobs[1].res_first_only = 0;
+    jobs[1].res_coef = 2.0 * s->alpha / (g->Nbglob * g->Lb); jobs[1].res_base = 0.0;
+    XW_TRY(xw_ode_bwd_multi(jobs, 2, g->t, s->theta, s->method, g->L, g->d, s->H, s->K, s->m, 2 | (((g->narrow >> 4) & 1) ? 16 : 0),
+                            main_stream));
+    // ONE slab set, already weighted: coefB = 1 (no scal)
+    return xw_adam(s->theta, g->slabA, g->ns_u + g->ns_b, nullptr, nullptr, 0, nullptr, nullptr, s->m_u, s->v_u, s->step_u, -1, s->Pu,
+                   s->lr_u, s->beta1, s->beta2, s->eps, s->grad_u, s->lag_lo, s->lag_hi, adam_skip_field, s->lag_u, main_stream);
+  }
   if (have_i) {
     Side* sd = side_of_current_device();
     if (sd == nullptr) return XW_E_ARG;

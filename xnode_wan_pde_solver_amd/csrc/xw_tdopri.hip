@@ -501,7 +501,7 @@ extern "C" int xw_tdopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const do
   for (int i = 0; i < njobs; ++i) {
     const XwDopriSweepJob& j = jobs[i];
     if (!j.b.xT || !j.b.start || !j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || j.b.N < 1) return XW_E_ARG;
-    if (j.b.res_u != nullptr && j.b.ubar != nullptr) return XW_E_ARG;
+    if (!cot_job_ok(j.b)) return XW_E_ARG;
     if ((mode & 2) && !j.b.gslab) return XW_E_ARG;
     if ((mode & 1) && !(mode & 4) && (!j.b.gx || !j.b.gs)) return XW_E_ARG;
     P.blk0[i + 1] = P.blk0[i] + (j.b.N + 15) / 16;

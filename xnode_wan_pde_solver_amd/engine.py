@@ -320,6 +320,9 @@ class Engine:
         # tools/shard_streams.sh, ms per sub-step wide / compact: 256 paths (+ 256 boundary paths) 0.2489 / 0.2183, 512 0.2609 / 0.2244,
         # 1024 0.2829 / 0.2487, 1536 0.3190 / 0.3108, 2048 0.3490 / 0.3432, 2560 0.3931 / 0.3791, 3072 0.4173 / 0.4272, 4096 0.4698 / 0.4919
         self.compact_tiles = int(opt.compact_tiles)
+        # one GPU: the generator's interior sweeps A and B as ONE sweep over A + (2/I) B (_gen_front_merged); off = the two-sweep
+        # schedules below for every group (XW_MERGED_SWEEP=0: the same build measured both ways)
+        self.merged_sweep = bool(opt.merged_sweep)
         self.prio_drop = {'A': int(opt.prio_drop_A) if opt.prio_drop_A is not None else (3 if self.d <= 32 else 2),
                           'X': int(opt.prio_drop_X), 'F': int(opt.prio_drop_F), 'G': int(opt.prio_drop_G)}
         self.use_runner = opt.use_runner      # one C call per eager group sub-step (xw_substep_*)
@@ -1095,6 +1098,7 @@ class Engine:
                     self._exchange_cb = self._host_exchange()
                     st.exchange = ctypes_addr(self._exchange_cb)
         st.v_blocks, st.v_blocks_disc = self.v_blocks, self.v_blocks_disc
+        st.merged_sweep = int(self.merged_sweep)
         st.alpha, st.pollution = float(self.alpha), float(self.pollution)
         st.lr_u, st.lr_v = float(self.config['u_rate']), float(self.config['v_rate'])
         return st
@@ -1133,12 +1137,12 @@ class Engine:
             ji, jb = self._job(G, 'i'), (self._job(G, 'b') if G.Nb else None)
             joint = G.Nb and G.same_grid
             # (bit 2: the runner launches sweep A, the boundary sweep on the same grid and sweep B as ONE launch -- the tile count
-            #  that decides is that launch's, as in _gen_front_compact; bit 4 is unused)
+            #  that decides is that launch's, as in _gen_front_compact; bit 4: the merged form's launch {interior kind 3, boundary})
             bits = [nar([ji] + ([jb] if joint else []), alone=False, forward=True),
                     bool(jb) and nar([jb], alone=False, forward=True),
                     nar([ji] + ([jb] if joint else []) + [ji], alone=False),
                     bool(jb) and nar([jb], alone=False),
-                    False,
+                    bool(joint) and nar([ji, jb], alone=False),
                     nar([ji], alone=False, params=False),
                     nar([ji], alone=False, forward=True),
                     nar([ji], alone=False, params=False)]
@@ -1219,8 +1223,10 @@ class Engine:
         self._gen_back(G)
 
     def _gen_front(self, G):
-        """everything up to (not including) the exchange: leaves slabA, slabB and scal[0..3] complete.
-        Kernel chains:  main   test network v, dv/dt and (fused) nabla_x v(t_0) -> cotangent B = dI/du -> parameter
+        """everything up to (not including) the exchange: leaves slabA, slabB and scal[0..3] complete (the merged form,
+        _gen_front_merged: slabA and scal[0..3] only -- slabB is not written, G.merged tells _gen_back).
+        Kernel chains of the wide schedule:
+                        main  test network v, dv/dt and (fused) nabla_x v(t_0) -> cotangent B = dI/du -> parameter
                                sweep B -> [join] -> I, sum v^2, SSE, loss values            (the critical path: one stream,
                                dependent launches of one stream follow each other without the ~10 us cross-queue hop)
                         side 1 u-forward (interior + boundary, one launch) -> boundary residual -> cotangent A
@@ -1232,6 +1238,9 @@ class Engine:
         fused_x = self.pollution == 1.0 and not self.adjoint
         joint = G.Nb and G.same_grid           # boundary paths on the interior's time grid: one launch for both
         e_x = None
+        G.merged = self._merged_ok(G, fused_x, joint)
+        if G.merged:
+            return self._gen_front_merged(G)
         if self._compact(G, fused_x, joint):
             return self._gen_front_compact(G)
         if not getattr(G, 'skip_v', False):
@@ -1341,6 +1350,54 @@ class Engine:
         G.sumA_ready = False
         self._contract(G, self.adam_u, with_bdry=True)
 
+    def _merged_ok(self, G, fused_x, joint):
+        """does this group's generator sub-step take the merged form?  One GPU, no carried gradient, the fused helper backward,
+        boundary paths on the interior's grid, no pairwise sums, a = identity and b = 0 (the same rule as xw_substep_gen's; every
+        stepper family forms the merged cotangent, XwOdeBwdJob.res_first_only == 3)"""
+        return bool(self.merged_sweep and self._world_of(G) is None and self.accum_u is None and fused_x and joint
+                    and not (G.pair_i or G.pair_b) and G.A0 is None and G.B0 is None)
+
+    def _gen_front_merged(self, G):
+        """_gen_front with ONE interior parameter sweep.  The update needs J^T A + (2/I) J^T B = J^T (A + (2/I) B): once I is on the
+        device the sweep forms the summed cotangent itself (kind 3) and the interior paths are swept once with weight gradients,
+        not twice.  I needs nabla_x u(t_0): an x-only sweep (one wave per tile, no partner wave, no slabs) delivers it beside the
+        test network, as in the discriminator sub-step.
+        Kernel chains:  main   test network -> [join] -> I, sum v^2, SSE, loss values -> sweeps {interior kind 3, boundary} (one
+                               launch, one slab set) -> Adam (in _gen_back)
+                        side 1 u-forward (interior + boundary, full store) -> x-only sweep from the store
+        One cross-queue edge; the same launches in the same order whether captured, eager or issued by xw_substep_gen.
+        Tile layout: every launch here asks _narrow_ok with alone=False, also when the test network is reused (skip_v) and the
+        launches do have the chip to themselves -- the `narrow_tiles_alone` thresholds, which _gen_front_compact applies in that
+        case, do NOT apply under the merged form.  The runner holds one precomputed layout bit per launch (XwGroup.narrow), and the
+        two layouts sum in different orders, so a second set of thresholds would have to reach both to keep reuse on / off and
+        runner / launch-by-launch bit-identical; not done, and not measured (at the headline only the x-only sweep, 256 tiles,
+        would change layout)."""
+        th = self.theta.data
+        M = (self.method, self.H, self.K, self.m)
+        lone = bool(getattr(G, 'skip_v', False))      # (only decides whether the test network is evaluated)
+        e0 = self._mark()
+        if not lone:
+            self._launch_test_net_here(G)
+        with self._side(1, e0):
+            fwd = [self._job(G, 'i'), self._job(G, 'b')]
+            self._ode_fwd_multi(fwd, G.t, th, *M, zero16=self.scal, narrow=self._narrow_ok(fwd, alone=False, forward=True),
+                             prio_drop=self.prio_drop['G'])
+            self._reaction(G)
+            sweep_x = [self._job(G, 'i', want_x=True)]
+            self._ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False,
+                             narrow=self._narrow_ok(sweep_x, alone=False, params=False))
+            e_x = self._mark()
+        self._join(e_x)
+        self._contract(G, self.adam_u, with_bdry=True)           # -> scal[0] = I, loss values, the optimiser's counter
+        res_M = dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob,
+                     weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck),
+                     merged=dict(ref=G.h, coef=2.0 * self.alpha / G.Nglob, base=self.pollution, scal=self.scal))
+        res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
+        sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u]), res=res_M),
+                  dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
+        self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=False, want_params=True, narrow=self._narrow_ok(sweeps, alone=False))
+        G.sumA_ready = False
+
     def begin_substep(self, which, accumulate):
         """start of a generator ('u') / discriminator ('v') sub-iteration over several groups: zero the carried gradient"""
         name, P = ('accum_u', self.Pu) if which == 'u' else ('accum_v', self.Pv)
@@ -1363,7 +1420,10 @@ class Engine:
                 KN.pair_fold(self.scal, G.Vol, G.Nglob)
             KN.losses(self.scal, G.L, G.Lb, G.Vol, G.Nglob, G.Nbglob, self.alpha, step=st['step'], init_off=G.init_off,
                       bdry_off=G.bdry_off)
-        if world is None and getattr(G, 'sumA_ready', False) and acc is None:
+        if world is None and getattr(G, 'merged', False):
+            # one slab set, weighted inside the sweep: no scal, coefB = 1
+            KN.adam(self.theta.data, G.slabA, st['m'], st['v'], st['step'], lr, gsum_out=self.grad_u, bump_step=-1, **lag)
+        elif world is None and getattr(G, 'sumA_ready', False) and acc is None:
             KN.adam(self.theta.data, None, st['m'], st['v'], st['step'], lr, gslabB=G.slabB, scal=self.scal,
                     gextraA=G.sumA, gsum_out=self.grad_u, bump_step=-1, **lag)
         elif world is None:

@@ -256,6 +256,13 @@ def _set_res(a, j, L, N):
             a.res_first_only, a.res_u, a.res_ref = 2, _p(res['u']), _p(res['ref'])
             a.res_w_per_point, a.res_w, a.res_c, a.res_cp = int(wpp), _p(wk['w']), _p(wk.get('c')), _p(wk.get('cp'))
             a.res_kappa2 = 2.0 * float(wk.get('ckappa', 0.0))
+            mg = res.get('merged')
+            if mg is not None:
+                # kind 3: [base_A + coef_A (u - ref_A) at l = 0] + (2 / scal[0]) (the weak form above) -- one interior sweep for
+                # the generator's cotangents A and B once I = scal[0] is on the device (XwOdeBwdJob.res_first_only == 3)
+                _chk(mg.get('ref'), F64, (N,), 'res.merged.ref'); _chk(mg.get('scal'), F64, None, 'res.merged.scal')
+                a.res_first_only, a.res_scal, a.res_refA = 3, _p(mg.get('scal')), _p(mg.get('ref'))
+                a.res_coefA, a.res_baseA = float(mg['coef']), float(mg['base'])
         else:
             first = bool(res['first_only'])
             _chk(res['u'], F64, (L, N), 'res.u'); _chk(res['ref'], F64, (N,) if first else (L, N), 'res.ref')
@@ -267,6 +274,8 @@ def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_on
     """jobs: list of dicts(xT, start, Y, ubar or None, gx, gs, gslab); ONE launch for all groups.
     res = dict(u[L,N], ref ([N] with first_only, else [L,N]), coef, base, first_only) instead of ubar: the cotangent
     base + coef (u - ref) (at l = 0 only with first_only) is formed inside the sweep.
+    res = dict(u, ref=v, coef, base, weak=dict(w, c, cp, ckappa)): the weak form's dI/du; with merged=dict(ref=h[N], coef, base,
+    scal[16]) on top: (the first_only form of `merged`) + (2 / scal[0]) dI/du, the generator's two interior sweeps as one.
     x_cot_ones (with want_x and want_params): gx, gs for the all-ones cotangent, parameter gradients for ubar, which must
     equal 1 at every time index >= 1; jobs without gx / gs produce no x outputs.
     adjoint: the continuous adjoint of torchdiffeq.odeint_adjoint (config['adjoint'] = True) instead of the reverse of

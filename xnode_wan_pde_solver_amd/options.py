@@ -38,6 +38,7 @@ class EngineOptions:
     narrow_tiles: Optional[str] = None  # XW_NARROW_TILES: "f:x:p" largest launches (16-path tiles) that still go narrow
     narrow_tiles_alone: str = '256:256:64'   # XW_NARROW_TILES_ALONE: the same for a launch that has the chip to itself (test network reused)
     early_slab_sum: bool = True         # XW_EARLY_SLAB_SUM
+    merged_sweep: bool = True           # XW_MERGED_SWEEP: one GPU -- the generator's interior sweeps A and B as ONE sweep over A + (2/I) B
     compact_tiles: int = 320            # XW_COMPACT_TILES: groups up to this many tiles take the compact generator schedule
     prio_drop_A: Optional[int] = None   # XW_PRIO_DROP_A: wave-priority drop of the generator's sweeps A + boundary (None: 3 up to d = 32, 2 above)
     prio_drop_X: int = 0                # XW_PRIO_DROP_X: ... of the discriminator's x-only sweep
@@ -86,6 +87,7 @@ class EngineOptions:
         o.narrow_tiles = os.environ.get('XW_NARROW_TILES') or None
         o.narrow_tiles_alone = os.environ.get('XW_NARROW_TILES_ALONE') or o.narrow_tiles_alone
         o.early_slab_sum = _flag('XW_EARLY_SLAB_SUM', o.early_slab_sum)
+        o.merged_sweep = _flag('XW_MERGED_SWEEP', o.merged_sweep)
         o.compact_tiles = _int('XW_COMPACT_TILES', o.compact_tiles)
         o.prio_drop_A = _int('XW_PRIO_DROP_A', None)
         o.prio_drop_X = _int('XW_PRIO_DROP_X', o.prio_drop_X)
