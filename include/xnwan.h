@@ -145,6 +145,24 @@ int xw_tiled_ode_fwd_multi(const XwOdeFwdJob* jobs, int njobs, const double* t, 
 int xw_tiled_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const double* theta,
                            int method, int L, int d, int H, int K, int m, int mode, double* work, void* stream);
 
+/* ---- the tiled family's forward pass over a RAGGED group (csrc/xw_tiled_paths.hip): every path on a time grid of its own -------
+ * Path p of a job has the spatial point xT[.][p], the start value start[p] and its own non-decreasing times tT[l][p], l < L
+ * (time-major, [L][N]); a path with fewer than L - 1 steps repeats its last time (a zero-length step is the exact identity of
+ * euler, midpoint and rk4, so the padded rows equal the path's final value).  u[l][p] is what xw_tiled_ode_fwd_multi gives for
+ * the one-path job (x_p, start_p) on the grid tT[.][p]; a job whose paths all carry one grid gives its bits.
+ *   nstep     : NULL, or int[N]: the index of each path's last distinct time (0 .. L - 1).  A 16-path tile steps max(nstep) times
+ *               and fills the later rows without evaluating the field; smaller values than the true ones give wrong rows.
+ *   last_only : != 0: only the final row is stored -- u is [N] (and Y, if given, [H][N])
+ *   Y         : NULL, or the states [L][H][N]
+ * Widths, theta and methods 0..2 as xw_tiled_ode_fwd_multi (other method ids: XW_E_ARG; xw_tiled_ode_ok == 0: XW_E_DIMS); the
+ * workspace is xw_paths_tiled_work(...) doubles per 16-path tile of every job of the launch (jobs in order).  No float atomics,
+ * no host synchronisation: the launch can be captured. */
+typedef struct { const double* xT; const double* start; const double* tT; const int* nstep; double* u; double* Y; int N;
+                 int last_only; } XwPathsJob;
+int xw_paths_tiled_work(int d, int H, int K, int m);
+int xw_paths_tiled_fwd(const XwPathsJob* jobs, int njobs, const double* theta, int method, int L, int d, int H, int K, int m,
+                       double* work, void* stream);
+
 /* ---- solver 'explicit_adams' on the tiled family: torchdiffeq's fixed-grid Adams-Bashforth (fixed_adams.py, implicit=False) ---
  * On the requested grid: f_n = F(t_n, y_n) joins a history of at most 11 field values; steps 0 and 1 are rk4 steps (3/8 rule,
  * method 2) with k1 = f_n, step n >= 2 is y_{n+1} = y_n + sum_{j < ord} dt_n beta[ord][j] f_{n-j}, ord = min(n + 1, 11) (AB3 ..

@@ -29,6 +29,11 @@ class XwOdeBwdJob(ctypes.Structure):
                 ('res_coefA', ctypes.c_double), ('res_baseA', ctypes.c_double)]
 
 
+class XwPathsJob(ctypes.Structure):       # include/xnwan.h: one ragged group of xw_paths_tiled_fwd (a time grid per path)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('tT', c_vp), ('nstep', c_vp), ('u', c_vp), ('Y', c_vp), ('N', c_int),
+                ('last_only', c_int)]
+
+
 class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
     _fields_ = [('xT', c_vp), ('start', c_vp), ('u', c_vp), ('Y', c_vp), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp),
                 ('fbuf', c_vp), ('ctl', c_vp), ('work', c_vp), ('N', c_int), ('cap', c_int)]
@@ -80,6 +85,8 @@ SIGNATURES = {
                                c_f64p, c_vp],
     'xw_tiled_ode_bwd_multi': [ctypes.POINTER(XwOdeBwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                c_f64p, c_vp],
+    'xw_paths_tiled_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_tiled_fwd': [ctypes.POINTER(XwPathsJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p, c_vp],
     'xw_adams_coef': [c_int, c_vp],
     'xw_adams_tiled_work': [c_int, c_int, c_int, c_int, c_int],
     'xw_adams_tiled_fwd_multi': [ctypes.POINTER(XwOdeFwdJob), c_int, c_f32p, c_f64p, c_int, c_int, c_int, c_int, c_int, c_f64p, c_f64p,

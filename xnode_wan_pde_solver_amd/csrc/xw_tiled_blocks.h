@@ -209,6 +209,20 @@ __device__ void tcomb(int H, double* dst, const double* s0, double c1, const dou
   sync_tile();
 }
 
+// ---- per-path siblings (xw_tiled_paths.hip): every path of the tile on a time grid of its own ---------------------------------
+// The time t_p and the coefficients c*_p are PER LANE: the value of the lane's own path, column lane & 15.  tgemm's epilogue
+// (e = r * 16 + (lane & 15)) and tcomb's loop (e = lane + 64 i) touch columns e & 15 == lane & 15 only, so the originals, handed a
+// lane's own value, ARE the per-path forms: the same operations in the same order -- bias, fma(tcol[r], t_p, .), add;
+// fma(c_p, s1[e], v) -- and, on a tile whose 16 paths carry one grid, the same bits as with the scalar.  (tfield hands its time
+// to the time term of z_0's tgemm and nowhere else.)
+__device__ __forceinline__ void tfield_pp(const Net& n, const TileWork& w, double* ws, double t_p, const double* yin, double* fo) {
+  tfield(n, w, ws, t_p, yin, fo, false);
+}
+__device__ __forceinline__ void tcomb_pp(int H, double* dst, const double* s0, double c1_p, const double* s1, double c2_p = 0.0,
+                                         const double* s2 = nullptr, double c3_p = 0.0, const double* s3 = nullptr) {
+  tcomb(H, dst, s0, c1_p, s1, c2_p, s2, c3_p, s3);
+}
+
 __device__ __forceinline__ void set_prio(int drop) {
   switch (3 - (drop & 3)) {
     case 0: __builtin_amdgcn_s_setprio(0); break;

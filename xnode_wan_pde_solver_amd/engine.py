@@ -1743,3 +1743,32 @@ class Engine:
         s = self.funcs['h'](Xd[:, 0, :]) if starts_T0 else self.funcs['g'](Xd[:, 0, :].unsqueeze(1)).reshape(-1)
         return self._u_forward(Xd[:, 0, 1:].to(self.dev).to(F64).t().contiguous(), Xd[0, :, 0].to(self.dev).to(F64).contiguous(),
                                s.detach().to(self.dev).to(F64).reshape(-1).contiguous())
+
+    def predict_paths(self, X, starts=None):
+        """u_theta on a RAGGED group [N, L, 1 + d] -> [L, N]: every path integrates over its OWN time channel X[i, :, 0]
+        (non-decreasing; a shorter path repeats its last time, and its padded rows hold its final value), x from slice 0 as the
+        module reads it.  starts [N]: the start values; None: per path h where X[i, 0, 0] == T0, else g -- the batched form of
+        evaluating [[x0, x]] point by point.  On the tiled family's per-path kernel (kernels.tiled_paths_fwd) at the blob's
+        widths, whichever family trains; fixed-grid schemes only; EngineOptions.eval_chunk_paths paths per launch."""
+        from . import evalpaths
+        if self.method not in KN.METHODS.values():
+            raise XnwanError("predict_paths: solver %r is not served -- per-path time grids run the fixed-grid schemes %s only"
+                             % (self.config['solver'], sorted(KN.METHODS)))
+        with torch.no_grad():
+            Xd = X.detach()
+            if Xd.dim() != 3 or Xd.shape[2] != 1 + self.d:
+                raise XnwanError('predict_paths: X must be [N, L, 1 + d] = [N, L, %d]' % (1 + self.d))
+            tT = Xd[:, :, 0].to(self.dev).to(F64).t().contiguous()
+            if starts is None:
+                first = Xd[:, 0, :]
+                at_T0 = first[:, 0] == self.setup['T0']
+                if bool(at_T0.all()):
+                    starts = self.funcs['h'](first)
+                else:
+                    starts = torch.where(at_T0, self.funcs['h'](first).reshape(-1), self.funcs['g'](first.unsqueeze(1)).reshape(-1))
+            if tT.shape[0] > 1 and bool((tT[1:] < tT[:-1]).any()):      # (the one device-side check)
+                raise XnwanError('predict_paths: the times of a path must not decrease')
+            return evalpaths.paths_forward(Xd[:, 0, 1:].to(self.dev).to(F64).t().contiguous(), tT,
+                                           starts.detach().to(self.dev).to(F64).reshape(-1).contiguous(), evalpaths.last_distinct(tT),
+                                           self.theta.data, self.method, self.H, self.K, self.m,
+                                           chunk=self.options.eval_chunk_paths)

@@ -1,0 +1,110 @@
+"""u_theta at scattered space-time points: every point is the end of a path of its own, on a time grid of its own.
+
+The stepper entry points take ONE grid t[L] for all paths of a job; kernels.tiled_paths_fwd (csrc/xw_tiled_paths.hip) takes a
+grid per path.  This module is the host side of it: the per-point grids (step_counts, pack_grids), the sort that makes the 16-path
+tiles homogeneous in their step count (sort_by_steps), the chunked launch (paths_forward) and the evaluation itself
+(evaluate_points, behind XNODE.evaluate / NODE_WAN_solver.evaluate).
+
+A point (t, x) is entered at (t_in, x) -- the domain class's `entry` rule: T0 with the start value h, or the moving boundary
+with g -- and integrated over n = max(1, ceil((t - t_in) / ((T - T0) / n_sub))) equal steps that end exactly at t; t == t_in takes
+none.  No gradients, no collective calls, no random numbers."""
+import torch
+
+from . import kernels as KN
+from ._lib import XnwanError
+
+F64 = torch.float64
+EVAL_CHUNK_PATHS = 65536                   # EngineOptions.eval_chunk_paths
+REFUSED_SOLVERS = ('dopri5', 'explicit_adams')
+
+
+def step_counts(t, t_in, T0, T, n_sub):
+    """steps per point, int64 [M]: 0 where t == t_in, else max(1, ceil((t - t_in) / ((T - T0) / n_sub))); t, t_in float64"""
+    step = (T - T0) / n_sub
+    n = torch.ceil((t - t_in) / step).clamp(min=1).to(torch.int64)
+    return torch.where(t == t_in, torch.zeros_like(n), n)
+
+
+def pack_grids(t, t_in, n):
+    """the grids, time-major tT [max n + 1, M] float64: row l of point i is t_in + (t - t_in) l / n_i for l < n_i and t itself
+    from l = n_i on (the grid ends exactly at t; the rows behind it repeat it: zero-length steps)"""
+    L = int(n.max()) + 1 if n.numel() else 1
+    l = torch.arange(L, dtype=F64, device=t.device).view(L, 1)
+    grid = t_in.view(1, -1) + (t - t_in).view(1, -1) * l / n.clamp(min=1).to(F64).view(1, -1)
+    return torch.where(l >= n.view(1, -1), t.view(1, -1).expand(L, -1), grid).contiguous()
+
+
+def sort_by_steps(n):
+    """(order, inverse): order sorts the points by their step count (stable), inverse[order[k]] = k puts results back"""
+    order = torch.argsort(n, stable=True)
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(order.numel(), device=order.device)
+    return order, inverse
+
+
+def last_distinct(tT):
+    """nstep [N] int32 of a packed group tT [L, N]: the index of each path's last time that differs from the one before it"""
+    L = tT.shape[0]
+    if L == 1:
+        return torch.zeros(tT.shape[1], dtype=torch.int32, device=tT.device)
+    idx = torch.arange(1, L, device=tT.device).view(L - 1, 1)
+    return ((tT[1:] != tT[:-1]) * idx).amax(0).to(torch.int32)
+
+
+def paths_forward(xT, tT, start, nstep, theta, method, H, K, m, last_only=False, chunk=EVAL_CHUNK_PATHS):
+    """kernels.tiled_paths_fwd on N paths, at most `chunk` of them per launch (the launches share the stream and so the
+    workspace's memory: it is bounded by the chunk): u [L, N], or [N] with last_only"""
+    N, L = xT.shape[1], tT.shape[0]
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    if N <= chunk:
+        u = torch.empty((N,) if last_only else (L, N), dtype=F64, device=xT.device)
+        KN.tiled_paths_fwd([dict(xT=xT, start=start, tT=tT, nstep=nstep, u=u)], theta, method, H, K, m, last_only=last_only)
+        return u
+    parts = []
+    for lo in range(0, N, chunk):
+        hi = min(lo + chunk, N)
+        parts.append(paths_forward(xT[:, lo:hi].contiguous(), tT[:, lo:hi].contiguous(), start[lo:hi].contiguous(),
+                                   None if nstep is None else nstep[lo:hi].contiguous(), theta, method, H, K, m, last_only, chunk))
+    return torch.cat(parts, -1)
+
+
+def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta at points [M, 1 + d] (time first; host or device, float32 or float64) -> u [M] float64 on `device`.
+    domain: the domain class or an instance (only its classmethod `entry` is used: nothing is constructed, nothing is drawn)."""
+    if solver in REFUSED_SOLVERS:
+        raise XnwanError("evaluate(): solver %r is not served -- per-path time grids run the fixed-grid schemes %s only (no "
+                         "per-path step controller or multistep history is built)" % (solver, sorted(KN.METHODS)))
+    entry = getattr(domain, 'entry', None)
+    if entry is None:
+        name = getattr(domain, '__name__', type(domain).__name__)
+        raise XnwanError('evaluate(): the domain class %s has no entry(points, shape_param, T0, T) rule: where a point\'s path '
+                         'starts, and with which start value, is the domain\'s to say' % name)
+    d, T0, T = setup['dim'], setup['T0'], setup['T']
+    n_sub = setup['N_t'] if n_sub is None else n_sub
+    if n_sub < 1:
+        raise XnwanError('evaluate(): n_sub = %r, at least one step over [T0, T]' % (n_sub,))
+    if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 1 + d):
+        raise XnwanError('evaluate(): points must be a tensor [M, 1 + d] = [M, %d], time first' % (1 + d))
+    with torch.no_grad():
+        pts = points.detach().to(F64)
+        if pts.shape[0] == 0:
+            return torch.empty(0, dtype=F64, device=device)
+        t = pts[:, 0].contiguous()
+        t_in, at_T0 = entry(pts, setup['shape_param'], T0, T)
+        early = t < t_in
+        if bool(early.any()):
+            i = int(early.nonzero()[0])
+            raise XnwanError('evaluate(): %d points lie before their entry time (t >= t_in is the limit; first: point %d, t = %r, '
+                             't_in = %r)' % (int(early.sum()), i, float(t[i]), float(t_in[i])))
+        n = step_counts(t, t_in, T0, T, n_sub)
+        first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
+        if bool(at_T0.all()):
+            s = h(first).reshape(-1).double()
+        else:                               # (both callables on every point, then a select: the batched form of h(x0) / g(x0))
+            s = torch.where(at_T0, h(first).reshape(-1).double(), g(first.unsqueeze(1)).reshape(-1).double())
+        order, inverse = sort_by_steps(n)
+        tT = pack_grids(t[order], t_in[order], n[order]).to(device)
+        u = paths_forward(pts[order, 1:].t().contiguous().to(device), tT, s[order].contiguous().to(device),
+                          n[order].to(torch.int32).to(device), theta, method, H, K, m, last_only=True, chunk=chunk)
+        return u[inverse.to(device)]

@@ -5,7 +5,7 @@ Conventions (include/xnwan.h): point arrays are time-major [L, N]; coordinates a
 """
 import torch
 
-from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob
+from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 DOPRI5 = 3                                 # solver 'dopri5' (adaptive, dopri5_fwd / dopri5_sweep below): not a fixed-grid method id
@@ -422,6 +422,31 @@ def tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True):
     Y = torch.empty(L, H, N, dtype=F64, device=xT.device) if want_Y else None
     tiled_ode_fwd_multi([dict(xT=xT, start=start, u=u, Y=Y)], t, theta, method, H, K, m)
     return u, Y
+
+
+def tiled_paths_fwd(jobs, theta, method, H, K, m, last_only=False):
+    """the tiled family's forward pass over ragged groups (csrc/xw_tiled_paths.hip): job = dict(xT[d,N], start[N], tT[L,N] -- a
+    non-decreasing time grid per path, a shorter path repeating its last time --, u[L,N] (last_only: [N]), optional Y[L,H,N]
+    (last_only: [H,N]) and nstep[N] int32, the index of each path's last distinct time); theta at the widths (H, K), the generic
+    layout.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        _chk(j['u'], F64, (N,) if last_only else (L, N), 'u'); _chk(j.get('Y'), F64, (H, N) if last_only else (L, H, N), 'Y')
+        a.xT, a.start, a.tT, a.nstep, a.u, a.Y = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep')), _p(j['u']), _p(j.get('Y'))
+        a.N, a.last_only = N, 1 if last_only else 0
+    # (xw_paths_tiled_work is the forward workspace of the family, xw_tiled_ode_work(0, ...): one allocation helper for both)
+    work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), theta.device)
+    check(lib.xw_paths_tiled_fwd(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_fwd')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

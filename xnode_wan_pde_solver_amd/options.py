@@ -49,6 +49,7 @@ class EngineOptions:
     xproj_min_d: int = 45               # XW_XPROJ_MIN_D: the test network's input layer once per path from this d on
     tiled_stepper: str = 'beyond'       # XW_TILED_STEPPER: the tiled stepper family only where the others refuse ('beyond'), or also in
                                         # place of the generic path ('generic'; kernels.stepper_family)
+    eval_chunk_paths: int = 65536       # XW_EVAL_CHUNK_PATHS: paths per launch of Engine.predict_paths / solver.evaluate (bounds the tiled workspace)
     hw_queues: int = 4                  # GPU_MAX_HW_QUEUES as the HIP runtime sees it (a warning above 4: the schedule is laid out for 4)
     # ---- engine: semantics / checks ---------------------------------------------------------------------------------------
     verify_structure: bool = True       # XW_VERIFY_STRUCTURE: re-probe the coefficient structure every few samples
@@ -97,6 +98,7 @@ class EngineOptions:
         o.capture_exchange = _flag('XW_CAPTURE_EXCHANGE', o.capture_exchange)
         o.xproj_min_d = _int('XW_XPROJ_MIN_D', o.xproj_min_d)
         o.tiled_stepper = os.environ.get('XW_TILED_STEPPER') or o.tiled_stepper
+        o.eval_chunk_paths = _int('XW_EVAL_CHUNK_PATHS', o.eval_chunk_paths)
         try:
             o.hw_queues = _int('GPU_MAX_HW_QUEUES', o.hw_queues)
         except ValueError:

@@ -309,8 +309,20 @@ def fillt(inputs, T, T0, min_steps=5):
     return index, out
 
 
+def _entry_at_T0(points, T0):
+    """the entry rule of a domain every point of which is reached from T0: (t_in [M] = T0, at_T0 [M] = True)"""
+    return torch.full_like(points[:, 0], T0), torch.ones(points.shape[0], dtype=torch.bool, device=points.device)
+
+
 class Hypercube:
     """[bot, top]^d x [T0, T]; time-independent domain.  `top_bot` = (bot, top)."""
+
+    @classmethod
+    def entry(cls, points, shape_param, T0, T):
+        """where the path that ends at each point (t, x) of points [M, 1 + d] starts: (t_in [M], at_T0 [M] bool) -- at T0 with
+        the start value h, or at t_in on the moving boundary with g.  A classmethod: nothing is constructed (a domain object
+        draws its time grid).  The cube: always T0."""
+        return _entry_at_T0(points, T0)
 
     def __init__(self, top_bot, dim, T0, T, N_t):
         assert top_bot[1] > top_bot[0], "The hypercube needs to have volume"
@@ -457,6 +469,11 @@ class _NSphereBase:
 class NSphere_TCone(_NSphereBase):
     """{ |x| < r (1 - t) }: the ball shrinks linearly to a point at t = 1."""
 
+    @classmethod
+    def entry(cls, points, shape_param, T0, T):
+        """(Hypercube.entry) the cone only shrinks: a point inside it has been inside since T0"""
+        return _entry_at_T0(points, T0)
+
     def interior(self, N_r):
         pts = self._ball(N_r)
         tcol = self.times.repeat(N_r, 1).unsqueeze(2)
@@ -501,6 +518,15 @@ class NSphere_THourglass(_NSphereBase):
 
     def _half(self):
         return (self.T - self.T0) / 2
+
+    @classmethod
+    def entry(cls, points, shape_param, T0, T):
+        """(Hypercube.entry) bound_pad's rule, per point: T0 in the narrowing half (t < half) and for points that never left the
+        inner ball (|x| <= r half); the others re-entered through the moving boundary at time |x| / r"""
+        r, half = shape_param, (T - T0) / 2
+        rad = torch.sqrt(torch.sum(points[:, 1:] ** 2, dim=-1))
+        at_T0 = (points[:, 0] < half) | torch.le(rad, r * half)
+        return torch.where(at_T0, torch.full_like(rad, T0), rad / r), at_T0
 
     def interior(self, N_r):
         """Same groups, same order and the same bits as the reference's per-path loop (src/dataset.py:62-104), without the

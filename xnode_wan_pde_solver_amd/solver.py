@@ -256,6 +256,12 @@ class NODE_WAN_solver:
         self.engine.theta, self.engine.phi = self.u_net.module.blob, self.v_net.module.blob
         self.optimizer_u.blob, self.optimizer_v.blob = self.engine.theta, self.engine.phi
 
+    def evaluate(self, points, n_sub=None):
+        """the trained solution at scattered space-time points [M, 1 + d] (time first; host or device) -> u [M] on the solver's
+        device, in one launch chain (XNODE.evaluate: a time grid per point, setup['N_t'] steps over [T0, T] unless n_sub says
+        otherwise).  No gradients, no collective calls (every rank evaluates what it is given), no random numbers drawn."""
+        return self.u_net.module.evaluate(points, n_sub, chunk=self.options.eval_chunk_paths)
+
     # --------------------------------------------------------------------------------------------------------------
     def _new_domain(self):
         s = self.setup
