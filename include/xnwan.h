@@ -420,6 +420,11 @@ typedef struct {
   const double *start, *start_b, *h, *href, *f, *g, *w, *wt, *w0, *ghT, *gwx0T, *c, *cp, *A0, *B0;
   double *u, *ub, *Y, *Yb, *act, *act_b, *v, *vt, *gxv, *gtv, *gx, *gs, *vbar, *s3x, *vact, *slabA, *slabB, *slab_v, *work_i, *work_b;
   double *xproj;                  /* [64][N] ([96][N] / [128][N] at W = 96 / 128) or NULL: table of xw_disc_xproj -- the test network then runs as xw_disc_fwd_xproj (path mode) */
+  int xproj_current;              /* the table kept across sub-steps (it depends on phi and the sample only; path mode).  0: not kept -- formed at
+                                     the head of every test-network launch.  1, 2: kept -- xw_substep_disc without a carried gradient forms it
+                                     again right behind its update of phi, on the same stream; 2: the caller vouches that it is that of the
+                                     current phi and sample (formed where the sample was loaded, or by that launch), and the test-network
+                                     launch has no head launch; 1: it is not, formed at the head */
 } XwGroup;
 /* in-place float64 sum of buf[count] over the ranks, enqueued on `stream`: xw_allreduce's own signature */
 typedef int (*XwExchangeFn)(double* buf, int count, void* ctx, void* stream);

@@ -50,7 +50,8 @@ class XwGroup(ctypes.Structure):           # include/xnwan.h: one group of paths
                 + [(n, c_vp) for n in ('xT', 'xvT', 'xbT', 't', 'tb', 'tpp', 'xvT_pts', 'start', 'start_b', 'h', 'href', 'f', 'g', 'w',
                                        'wt', 'w0', 'ghT', 'gwx0T', 'c', 'cp', 'A0', 'B0', 'u', 'ub', 'Y', 'Yb', 'act', 'act_b', 'v',
                                        'vt', 'gxv', 'gtv', 'gx', 'gs', 'vbar', 's3x', 'vact', 'slabA', 'slabB', 'slab_v', 'work_i',
-                                       'work_b', 'xproj')])
+                                       'work_b', 'xproj')]
+                + [('xproj_current', c_int)])
 
 
 class XwSolverState(ctypes.Structure):

@@ -212,13 +212,17 @@ __global__ void __launch_bounds__(256, (W > 64 ? 1 : XW_DISC_FWD_WAVES)) k_disc_
     asm volatile("" : "+s"(pht));                                       // addresses out of the loop-invariant (spilled) set
     if (XPROJ) {
       // input layer from the path's x-projection (rows >= W of it are zero): a_0 = (Vin[:, 1..d] x + Vin.b) + Vin[:, 0] t
-      const double* xp = xproj + pt.n;
+      // (the row offsets (16 mt + 4 r + g) N do not change from tile to tile: formed HERE, from a copy of N the compiler cannot see
+      //  through -- hoisted out of the tile loop they stay live across the layers and go to scratch, like the fragment addresses above)
+      int Nl = N;
+      asm volatile("" : "+s"(Nl));
+      const double* xp = xproj + pt.n + (long)g * Nl;
 #pragma unroll
       for (int mt = 0; mt < D::MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           ad[mt][r] = sIn[16 * mt + g + 4 * r];
-          a[mt][r] = (16 * mt + 4 * r < W) ? fma(ad[mt][r], pt.t, xw_ld_g(xp + (long)(16 * mt + 4 * r + g) * N)) : 0.0;
+          a[mt][r] = (16 * mt + 4 * r < W) ? fma(ad[mt][r], pt.t, xw_ld_g(xp + (long)(16 * mt + 4 * r) * Nl)) : 0.0;
         }
     } else if (VINLDS) {
 #pragma unroll

@@ -51,7 +51,7 @@ int test_net(const XwGroup* g, const XwSolverState* s, int blocks, double* recor
   if (g->tpp != nullptr)
     return xw_disc_fwd(g->xvT_pts, nullptr, g->tpp, s->phi, g->N * g->L, 1, g->d, s->W, s->q, g->v, g->vt, g->gxv, g->gtv, g->N, blocks,
                        record, stream);
-  if (g->xproj != nullptr) XW_TRY(xw_disc_xproj(g->xvT, s->phi, g->N, g->d, s->W, g->xproj, stream));
+  if (g->xproj != nullptr && g->xproj_current != 2) XW_TRY(xw_disc_xproj(g->xvT, s->phi, g->N, g->d, s->W, g->xproj, stream));
   return xw_disc_fwd_xproj(g->xvT, g->t, nullptr, s->phi, g->N, g->L, g->d, s->W, s->q, g->v, g->vt, g->gxv, g->gtv, g->N, blocks, record,
                            g->xproj, stream);
 }
@@ -291,6 +291,10 @@ extern "C" int xw_substep_disc(const XwGroup* g, const XwSolverState* s, int ski
     XW_TRY(xw_adam(s->phi, accum, accum != nullptr ? 1 : 0, s->grad_v, nullptr, 0, nullptr, nullptr, s->m_v, s->v_v, s->step_v, -1, s->Pv,
                    s->lr_v, s->beta1, s->beta2, s->eps, s->grad_v, 0, 0, 0, nullptr, stream));
   }
+  // phi has just moved: the group's x-projection table for the sub-steps that follow, directly behind the update on the same stream
+  // (XwGroup.xproj_current; with a carried gradient phi moves again before this group's next sub-step)
+  if (have_i && g->xproj != nullptr && g->tpp == nullptr && g->xproj_current != 0 && accum == nullptr)
+    XW_TRY(xw_disc_xproj(g->xvT, s->phi, g->N, g->d, s->W, g->xproj, stream));
   if (accum != nullptr) {
     const hipError_t e = hipMemcpyAsync(accum, s->grad_v, sizeof(double) * s->Pv, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;

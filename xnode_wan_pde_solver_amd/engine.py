@@ -231,13 +231,27 @@ class Engine:
             warnings.warn('%s is outside the MFMA kernel instantiations %s (u_layers <= 10) / %s: running on the generic vector-ALU path, expect a step '
                           'rate lower by two to three orders of magnitude' % (which, KN.ODE_WIDTHS, KN.DISC_WIDTHS), RuntimeWarning, stacklevel=3)
         # the test network's input layer: spatial columns once per path (xw_disc_xproj) -- the MFMA widths, paths over a shared grid
-        # XW_XPROJ_MIN_D: from which d on.  In the sub-step cycle the split form wins from d ~ 45 on and not below, at 131072 points as at
-        # a million (profiles/r05_xproj.txt: headline d = 20 0.488 against 0.473 ms per sub-step -- the small launch is one more dependent
-        # node on the critical chain --, d = 20 at 16384 x 64 3.41 against 3.38; d = 50 -1.3 %, BASELINE configs[2] -2.7 %, [3] -6.5 %).
+        # XW_XPROJ_MIN_D: from which d on WITH the table formed at the head of the launch.  In that form the split wins in the sub-step
+        # cycle from d ~ 45 on and not below, at 131072 points as at a million (profiles/r05_xproj.txt: headline d = 20 0.488 against
+        # 0.473 ms per sub-step -- the small launch is one more dependent node on the critical chain --, d = 20 at 16384 x 64 3.41
+        # against 3.38; d = 50 -1.3 %, BASELINE configs[2] -2.7 %, [3] -6.5 %).  Below it the table is only used where it is kept
+        # across sub-steps and the head node is gone (xproj_cached, next paragraph).
         # (the tiled family hoists nothing: no table, at any width and depth)
         self.xproj_min_d = 1 << 30 if (self.generic[1] or self.testnet_tiled) else int(opt.xproj_min_d)
         if self.W > 64 and not self.generic[1] and not self.testnet_tiled:
             self.xproj_min_d = 0        # (the 128-wide container: 131 KB of Vh fragments leave no LDS for input-layer fragments -- always the table)
+        # XW_XPROJ_CACHED: the table depends on phi and on the sample only, and inside an outer iteration every sub-step of a group sees
+        # the same two -- so it is formed where the sample is loaded (load_group, refill_compact) and right behind the discriminator's
+        # Adam, on the same queue, and a test-network launch whose table is still current (_xproj_state, decided outside captured code
+        # like _v_fresh) has no head node.  Without the head node the hoisted main launch pays from xproj_cached_min_d on
+        # (profiles/r16_xproj_cached.md).  A table that is not current -- phi written from outside, invalidate_test_net(), the other
+        # groups of a sub-iteration over several groups, whose phi moves between their sub-steps -- is formed at the head as before.
+        # Only the group a discriminator sub-step runs on gets the launch behind Adam: a captured graph would bake in the buffers of
+        # whatever other groups were alive at capture time; their keys no longer match and they take the head launch.
+        # The groups of a list domain loaded in one piece (load_groups_packed: 11-20 per sample, phi moving between their discriminator
+        # sub-steps) keep no table below xproj_min_d: they run exactly as before.
+        self.xproj_cached = bool(opt.xproj_cached) and self.xproj_min_d < (1 << 30)
+        self.xproj_table_min_d = min(self.xproj_min_d, int(opt.xproj_cached_min_d)) if self.xproj_cached else self.xproj_min_d
         if self.generic[0] and self.adjoint:
             raise XnwanError('adjoint=True (the continuous adjoint) exists for the MFMA stepper instantiations %s only; u_hidden_dim = %d, '
                              'u_hidden_hidden_dim = %d run on the generic path, which reverses the steps taken (adjoint=False)'
@@ -705,6 +719,7 @@ class Engine:
                 G.domain = domain
                 G.__dict__.update(pair_state)
                 G.sample_version += 1
+                self._form_xproj(G)
                 return G
         G = Group()
         for k in Group.SAMPLE_FIELDS:
@@ -720,6 +735,7 @@ class Engine:
         # (a group of a list domain changes shape with every sample and is built anew each time: the count of samples it has seen
         #  is carried over, or the periodic structure guard above -- two read-backs -- would run on EVERY sample)
         G.sample_version = into.sample_version + 1 if into is not None else 0
+        self._form_xproj(G)
         return G
 
     def load_groups_packed(self, shards, hints, domain, cache, big):
@@ -764,7 +780,7 @@ class Engine:
                 fields += [('tpp', (L * N,)), ('tpp0', (N,)), ('xvT_pts', (d, L * N))]
             fields += [('start', (N,)), ('ghT', (d, N)), ('h', (N,)), ('f', (L, N)), ('w', (L, N)), ('wt', (L, N)), ('w0', (N,)), ('gwx0T', (d, N)),
                        ('tb', (Lb,)), ('xbT', (d, Nb)), ('start_b', (Nb,)), ('g', (Lb, Nb))]
-            self._work_buffers(G, fields)
+            self._work_buffers(G, fields, cached_table=False)
             G._lazy['xvT'] = G._lazy['xT']           # (the v sample of a list domain is the u sample)
             if shared:
                 G.tpp = G.tpp0 = G.xvT_pts = None
@@ -817,6 +833,8 @@ class Engine:
         tdev = pinned.to(dev, non_blocking=True)
         _PIN_POOL.uploaded(pinned, torch.cuda.current_stream(dev))
         KN.gather_fields(tdev, len(rows), total)
+        for G in groups:
+            self._form_xproj(G)
         # single-slice groups at T0: the reference's [N, N] broadcasts in factorised form (load_group); these read five sums back
         for G in groups:
             if G.pair_i and not st.b_zero:
@@ -837,7 +855,7 @@ class Engine:
                     G.bdry_off = sgg / G.Nbglob - (sg / G.Nbglob) ** 2
         return groups
 
-    def _work_buffers(self, G, fields):
+    def _work_buffers(self, G, fields, cached_table=True):
         """every buffer the sub-steps of G need, as regions of ONE allocation (Group._arena / _lazy), behind the regions `fields`
         = [(name, shape)] the caller fills itself (load_groups_packed: the sample fields)"""
         dev, d, N, L, Nb, Lb = self.dev, self.d, G.N, G.L, G.Nb, G.Lb
@@ -864,7 +882,9 @@ class Engine:
                 plan.append(('act_b', (max(Lb - 1, 1), ar, KN.ode_act_cols(Nb))))
         if keep_v:
             plan.append(('vact', (KN.disc_act_rows(self.W, self.q), KN.disc_act_cols(L * N))))
-        if N and d >= self.xproj_min_d:
+        # (below xproj_min_d the table only pays without its head launch: path-mode groups, whose table is cached)
+        point_mode = G.__dict__.get('tpp') is not None or any(n_ == 'tpp' for n_, _ in fields)
+        if N and (d >= self.xproj_min_d or (cached_table and d >= self.xproj_table_min_d and not point_mode)):
             plan.append(('xproj', (KN.disc_xproj_rows(self.W), N)))   # Vin[:, 1..d] x + Vin.b per path (_launch_test_net_here)
         if Nb:
             plan += [('ub', (Lb, Nb)), ('Yb', (Lb, H, Nb))]
@@ -916,6 +936,7 @@ class Engine:
         def body(_G):
             if lean:
                 self._refill_fields(G, td, du, dv, db, domain, t0)
+                self._form_xproj(G)      # (the new sample's table, part of the refill graph: outside every sub-step)
                 return
             out = self.load_group(_paths(td, du), _paths(td, dv), _paths(td, db), domain, n_glob, nb_glob, into=G, shared_grid_t0=t0,
                                   verify=False)
@@ -937,6 +958,8 @@ class Engine:
         self._run(G, key, body, scratch=True)
         # (host-side bookkeeping of load_group: done at capture time only, so it is set here on every path)
         G.domain, G.sample_version = domain, ver + 1
+        if self._xproj_held(G):
+            G.xproj_key = self._v_key(G)
         return G
 
     def _refill_fields(self, G, td, du, dv, db, domain, t0):
@@ -1023,7 +1046,10 @@ class Engine:
         else:
             # (the input layer's spatial columns do not move along a vertical path: applied once per path by a small launch in
             #  front, csrc/xw_disc.hip k_disc_xproj -- the main launch then loads its row of that table instead of x)
-            xp = KN.disc_xproj(G.xvT, ph, self.W, out=G.xproj) if 'xproj' in G._lazy else None
+            #  -- unless the group's table is still that of this phi and this sample: _xproj_state)
+            xp = None
+            if 'xproj' in G._lazy:
+                xp = G.xproj if getattr(G, 'xproj_cur', False) else KN.disc_xproj(G.xvT, ph, self.W, out=G.xproj)
             KN.disc_fwd(G.xvT, G.t, ph, self.W, self.q, v=G.v, vt=G.vt, gxv=G.gxv, gtv=G.gtv, ngrad=G.N,
                         max_blocks=blocks, act=act, xproj=xp)
 
@@ -1148,6 +1174,7 @@ class Engine:
                     nar([ji], alone=False, params=False)]
             xg.narrow = sum(1 << i for i, b in enumerate(bits) if b)
         xg.sharded = int(bool(getattr(G, 'sharded', False)))
+        xg.xproj_current = (2 if getattr(G, 'xproj_cur', False) else 1) if self._xproj_held(G) else 0
         xg.pair_i, xg.pair_b = int(bool(G.pair_i)), int(bool(G.pair_b))
         xg.Vol, xg.Nglob, xg.Nbglob, xg.s3_scale = float(G.Vol), float(G.Nglob), float(G.Nbglob), float(G.s3_scale)
         xg.init_off, xg.bdry_off, xg.ckappa = float(G.init_off), float(G.bdry_off), float(self.structure.c_kappa)
@@ -1438,6 +1465,43 @@ class Engine:
         if acc is not None:
             acc.copy_(self.grad_u)
 
+    def xproj_plan(self):
+        """how the test network's input layer treats the spatial columns on path-mode groups (solver.plan())"""
+        if self.xproj_min_d >= (1 << 30):
+            return 'per point (the %s test-network family has no x-projection table)' % ('tiled' if self.testnet_tiled else 'generic')
+        if self.d < self.xproj_table_min_d:
+            return 'per point (d = %d: the x-projection table is used from d = %d on)' % (self.d, self.xproj_table_min_d)
+        if self.xproj_cached:
+            return ('x-projection table per path, cached (from d = %d on): formed where the sample is loaded and behind the '
+                    'discriminator\'s update, at the head of a launch only when phi or the sample changed otherwise' % self.xproj_table_min_d)
+        return 'x-projection table per path, formed at the head of every test-network launch (from d = %d on)' % self.xproj_table_min_d
+
+    def _xproj_held(self, G):
+        """does the engine keep G's x-projection table current across sub-steps?  (path mode, caching on)"""
+        return self.xproj_cached and G.N > 0 and G.tpp is None and 'xproj' in G._lazy
+
+    def _form_xproj(self, G):
+        """G's table from the current phi and sample, on the current stream, and the key it then stands for (called where the
+        sample is loaded; the key is host-side bookkeeping like _v_fresh's)"""
+        if self._xproj_held(G):
+            KN.disc_xproj(G.xvT, self.phi.data, self.W, out=G.xproj)
+            G.xproj_key = self._v_key(G)
+
+    def _xproj_tail(self, G):
+        """is G's table formed again right behind the discriminator's Adam?  Static per group, but for the carried gradient of a
+        sub-iteration over several groups: there phi moves again before G's next sub-step and the launch would be for nothing"""
+        return self._xproj_held(G) and self.accum_v is None
+
+    def _xproj_state(self, G, now):
+        """python-side bookkeeping (outside the captured graphs): is G's table that of the current phi and sample (`now` = _v_key)?
+        Sets G.xproj_cur for the test-network launch of this sub-step -- current: no head launch -- and returns the graph-key suffix"""
+        G.xproj_cur = False
+        if G.skip_v or not self._xproj_held(G):
+            return ''
+        G.xproj_cur = getattr(G, 'xproj_key', None) == now
+        G.xproj_key = now                # (not current: this sub-step forms it at the head)
+        return '_xc' if G.xproj_cur else ''
+
     def _v_fresh(self, G, store=False):
         """python-side bookkeeping (outside the captured graphs): are the test-network outputs of this group still those
         of the current phi and sample?  Sets G.skip_v for the front segment and returns the graph-key suffix."""
@@ -1446,7 +1510,7 @@ class Engine:
         G.v_version = now
         if not G.skip_v:                 # this sub-step evaluates the test network: does it leave the layer inputs behind?
             G.vact_valid = G.vact is not None and (store or self.reuse_test_net)
-        return ('_vcached' if G.skip_v else '') + ('_act' if getattr(G, 'vact_valid', False) else '')
+        return ('_vcached' if G.skip_v else '') + ('_act' if getattr(G, 'vact_valid', False) else '') + self._xproj_state(G, now)
 
     def _v_key(self, G):
         """(engine-side updates of phi, torch-side in-place writes to its parameters, resamples of the group)"""
@@ -1467,6 +1531,15 @@ class Engine:
 
     def generator_step(self, G):
         """one pass of the generator sub-step body; loss_u is left in scal[4] (device)"""
+        try:
+            self._generator_step(G)
+        except BaseException:
+            G.xproj_key = None           # (what the bookkeeping promised may not have been launched)
+            raise
+        finally:
+            G.xproj_cur = False          # (a test-network launch outside a sub-step forms its table at the head)
+
+    def _generator_step(self, G):
         sfx = self._v_fresh(G)
         world = self._world_of(G)
         if self._runner_ok(G):
@@ -1574,6 +1647,10 @@ class Engine:
             if acc is not None:
                 self.grad_v.add_(acc)
             KN.adam(self.phi.data, None, st['m'], st['v'], st['step'], lr, gextraA=self.grad_v, bump_step=-1)
+        if self._xproj_tail(G):
+            # phi has just moved: G's table for the sub-steps that follow, on the same queue directly behind the update (a same-queue
+            # successor starts without a gap; at the head of the next sub-step it would be one more dependent node of its critical chain)
+            KN.disc_xproj(G.xvT, self.phi.data, self.W, out=G.xproj)
         if acc is not None:
             acc.copy_(self.grad_v)
 
@@ -1599,8 +1676,24 @@ class Engine:
 
     def discriminator_step(self, G):
         """one pass of the discriminator sub-step body; loss_v is left in scal[5] (device)"""
+        try:
+            self._discriminator_step(G)
+        except BaseException:
+            G.xproj_key = None
+            raise
+        finally:
+            G.xproj_cur = False
+
+    def _disc_bookkeeping(self, G):
+        """host side of a discriminator sub-step, outside captured code: the graph-key suffix, phi's version, the table's key"""
         sfx = self._v_fresh(G, store=True)
         self._phi_version += 1                                    # phi changes at the end of this sub-step
+        if self._xproj_tail(G):
+            G.xproj_key = self._v_key(G)                          # ... and G's table is formed again right behind that update
+        return sfx
+
+    def _discriminator_step(self, G):
+        sfx = self._disc_bookkeeping(G)
         world = self._world_of(G)
         if self._runner_ok(G):
             from ._lib import lib

@@ -46,7 +46,11 @@ class EngineOptions:
     prio_drop_G: int = 0                # XW_PRIO_DROP_G: ... of the generator's forward pass
     use_runner: bool = True             # XW_RUNNER: one C call per eager group sub-step (xw_substep_*)
     capture_exchange: bool = True       # XW_CAPTURE_EXCHANGE: several GPUs on RCCL -- the exchange inside the sub-step graphs
-    xproj_min_d: int = 45               # XW_XPROJ_MIN_D: the test network's input layer once per path from this d on
+    xproj_min_d: int = 45               # XW_XPROJ_MIN_D: the test network's input layer once per path from this d on, even with the table
+                                        # formed at the head of every test-network launch
+    xproj_cached: bool = True           # XW_XPROJ_CACHED: that table is kept per group while phi and the sample stand (formed where the
+                                        # sample is loaded and right behind the discriminator's Adam, not at the head of a sub-step) ...
+    xproj_cached_min_d: int = 20        # XW_XPROJ_CACHED_MIN_D: ... and then used from this d on (profiles/r16_xproj_cached.md)
     tiled_stepper: str = 'beyond'       # XW_TILED_STEPPER: the tiled stepper family only where the others refuse ('beyond'), or also in
                                         # place of the generic path ('generic'; kernels.stepper_family)
     eval_chunk_paths: int = 65536       # XW_EVAL_CHUNK_PATHS: paths per launch of Engine.predict_paths / solver.evaluate (bounds the tiled workspace)
@@ -97,6 +101,8 @@ class EngineOptions:
         o.use_runner = _flag('XW_RUNNER', o.use_runner)
         o.capture_exchange = _flag('XW_CAPTURE_EXCHANGE', o.capture_exchange)
         o.xproj_min_d = _int('XW_XPROJ_MIN_D', o.xproj_min_d)
+        o.xproj_cached = _flag('XW_XPROJ_CACHED', o.xproj_cached)
+        o.xproj_cached_min_d = _int('XW_XPROJ_CACHED_MIN_D', o.xproj_cached_min_d)
         o.tiled_stepper = os.environ.get('XW_TILED_STEPPER') or o.tiled_stepper
         o.eval_chunk_paths = _int('XW_EVAL_CHUNK_PATHS', o.eval_chunk_paths)
         try:

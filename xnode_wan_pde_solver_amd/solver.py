@@ -490,6 +490,7 @@ class NODE_WAN_solver:
                         'tiled': 'tiled MFMA family (csrc/xw_tiled.hip)'}[eng.stepper],
             'testnet': ('tiled MFMA family at width %d (csrc/xw_disc_tiled.hip)' % eng.W if eng.testnet == 'tiled' else
                         'generic vector-ALU path (csrc/xw_generic.hip)' if eng.generic[1] else 'fused MFMA container %d' % eng.W),
+            'testnet_input_layer': eng.xproj_plan(),
             'ranks': 1 if self.world is None else self.world.size,
             'exchange': None if self.world is None else ('xw_allreduce (RCCL) on the stream: inside the sub-step graphs / the group runner'
                                                          if self.world.capturable else 'torch.distributed, staged through the host'),
