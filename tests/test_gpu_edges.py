@@ -1,7 +1,7 @@
 """Edge shapes of the wave-per-tile kernel families inside a guard-banded, poisoned arena (tests/guarded.py): the tiled stepper
 (csrc/xw_tiled.hip: euler, midpoint, rk4, explicit_adams), dopri5 on it (csrc/xw_tdopri.hip), the tiled test network
-(csrc/xw_disc_tiled.hip) and, under the same guards, the fused (64, 16) container, the narrow-tile sweeps and the 96 / 128
-test-network containers.
+(csrc/xw_disc_tiled.hip) and, under the same guards, the fused (64, 16) container, the narrow-tile sweeps and the test network's
+MFMA containers (96 / 128, and the 50 / 64 kernels of the flagship workload over a covering selection of their own).
 
 Every case
   * takes every operand -- inputs, outputs, slabs, and through guarded.Arena.workspaces the tiled families' workspaces -- from one
@@ -23,6 +23,8 @@ Regions pinned as untouched (from the code):
                                   want_x
   tiled test network              the record's columns of the points past N L in its last 16-point tile (only valid points store);
                                   vt, gxv, gtv where not requested are not passed at all
+  test-network MFMA containers    nothing: the record's padding columns ARE written (every lane of the ragged last tile stores a copy
+                                  of the last valid point into a slot of its own, csrc/xw_disc.hip k_disc_fwd): all of it is checked
   fused containers                nothing: the activation store's padding columns ARE written (padding paths hold copies and have
                                   slots of their own, csrc/xw_ode.hip act_store).  At (64, 16) every double row of the store is
                                   checked as written; at (20, 10) the partial 4-row block (K mod 4 = 2) leaves slots unused inside the
@@ -574,19 +576,25 @@ assert 60 <= len(TESTNET_CASES) <= 100, len(TESTNET_CASES)
 
 
 def _testnet_reference(W, q, d, mode, P_, seed):
-    """phi, the device operands' host values and the oracle's v, input gradient and parameter gradient"""
+    """phi, the device operands' host values and the oracle's v, input gradient and parameter gradient; P_: a key of POINTS"""
+    N, L = POINTS[P_] if mode == 'path' else (P_, 1)
+    return _testnet_reference_nl(W, q, d, mode, N, L, seed)
+
+
+def _testnet_reference_nl(W, q, d, mode, N, L, seed):
+    """_testnet_reference at N paths x L times (path mode) / N points (point mode, L = 1); shared with
+    tests/test_gpu_testnet_inventory.py"""
     from test_gpu_tiled_testnet import _phi, _reference
     cfg, phi = _phi(d, W, q, seed)
     g = torch.Generator().manual_seed(seed + 1)
     if mode == 'path':
-        N, L = POINTS[P_]
         x = torch.rand(N, d, generator=g, dtype=F64) * 2 - 1
         t, _ = torch.sort(torch.rand(L, generator=g, dtype=F64))
         X = torch.cat((t.view(1, L, 1).expand(N, L, 1), x.view(N, 1, d).expand(N, L, d)), 2).contiguous()
         vbar = torch.randn(N, L, dtype=F64, generator=g)
         tpp = None
     else:
-        N, L = P_, 1
+        assert L == 1
         x = torch.rand(N, d, generator=g, dtype=F64) * 2 - 1
         tpp = torch.rand(N, generator=g, dtype=F64)
         t = None
@@ -596,9 +604,14 @@ def _testnet_reference(W, q, d, mode, P_, seed):
     return phi, x, t, tpp, vbar, N, L, v_ref, gX, gphi
 
 
-def _run_testnet(W, q, d, mode, P_, ngrad_kind, family, seed, max_blocks):
+def _run_testnet(W, q, d, mode, P_, ngrad_kind, family, seed, max_blocks, table=False):
+    """P_: a key of POINTS, or (N, L) -- in point mode the N L points of it; table: the input layer through disc_xproj's table"""
     from xnode_wan_pde_solver_amd import kernels as KN
-    phi, x, t, tpp, vbar, N, L, v_ref, gX, gphi = _testnet_reference(W, q, d, mode, P_, seed)
+    if isinstance(P_, tuple):
+        N_, L_ = P_ if mode == 'path' else (P_[0] * P_[1], 1)
+        phi, x, t, tpp, vbar, N, L, v_ref, gX, gphi = _testnet_reference_nl(W, q, d, mode, N_, L_, seed)
+    else:
+        phi, x, t, tpp, vbar, N, L, v_ref, gX, gphi = _testnet_reference(W, q, d, mode, P_, seed)
     ngrad = {'0': 0, '1': 1, 'N': N}[ngrad_kind]
     arena = G.Arena(torch.device(DEVICE))
     xT = arena.inp(x.t(), name='xT')
@@ -610,7 +623,12 @@ def _run_testnet(W, q, d, mode, P_, ngrad_kind, family, seed, max_blocks):
     gtv = arena.out(ngrad, name='gtv') if ngrad else None
     rows, cols = KN.disc_act_rows(W, q, family), KN.disc_act_cols(N * L)
     act = arena.out(rows, cols, name='act')
-    KN.disc_fwd(xT, tc, blob, W, q, tpp=tp, v=v, vt=vt, gxv=gxv, gtv=gtv, ngrad=ngrad, max_blocks=max_blocks, act=act, family=family)
+    if table:
+        xp = arena.out(KN.disc_xproj_rows(W), N, name='xproj')
+        KN.disc_xproj(xT, blob, W, out=xp)
+        KN.disc_fwd(xT, tc, blob, W, q, v=v, vt=vt, gxv=gxv, gtv=gtv, ngrad=ngrad, max_blocks=max_blocks, act=act, xproj=xp, family=family)
+    else:
+        KN.disc_fwd(xT, tc, blob, W, q, tpp=tp, v=v, vt=vt, gxv=gxv, gtv=gtv, ngrad=ngrad, max_blocks=max_blocks, act=act, family=family)
     vb = arena.inp(vbar.t() if mode == 'path' else vbar.view(1, -1), name='vbar')
     slab = arena.out(KN.disc_bwd_slabs(N, L), blob.numel(), name='gslab')
     KN.disc_bwd(xT, tc, blob, vb, W, q, tpp=tp, gslab=slab, act=act, family=family)
@@ -622,7 +640,16 @@ def _run_testnet(W, q, d, mode, P_, ngrad_kind, family, seed, max_blocks):
         point = (torch.arange(cols // 16).view(-1, 1, 1) * 16 + torch.arange(16).view(1, 1, 16)).expand(cols // 16, rows, 16)
         written.append((rec, point < N * L))
         untouched.append((rec, point >= N * L))
+    else:
+        # the MFMA containers: every lane of the ragged last tile stores into a slot of its own (k_disc_fwd: the record's stores are
+        # not masked by the point's validity, and k_disc_rec reads those columns with a zero cotangent): all of it is written
+        written.append(act)
+    if table:
+        written.append(xp)
     arena.check(written=written, untouched=untouched)
+    if table:
+        _close(xp[:W].t(), x @ phi['Vin'][:, 1:].t() + phi['Vin_b'], TOL_VALUE, 'x projection')
+        assert float(xp[W:].abs().sum()) == 0.0, 'padding rows of the x projection'
     if mode == 'path':
         _close(v.t(), v_ref, TOL_VALUE, 'v')
         _close(vt.t(), gX[:, :, 0], TOL_TANGENT, 'dv/dt')
@@ -661,6 +688,39 @@ def test_tiled_testnet_edges(c):
 def test_wide_testnet_containers_under_guards(W, P_):
     i = tuple(POINTS).index(P_) + (W == 128)
     _run_testnet(W, (9, 1, 16, 4)[i % 4], (5, 1, 20)[i % 3], ('path', 'point')[i % 2], P_, ('N', '1', '0')[i % 3], 'mfma', 950 + i, 1 + i % 2)
+
+
+# the containers the benchmark runs (W = 50) and the one above it (64): forward with the fused gradient, record, reverse from it
+MFMA_POINTS = tuple(POINTS.values()) + ((64, 2), (128, 1))                    # (N, L); point mode: the N L points of it
+MFMA_AXES = {'W': (50, 64), 'q': (0, 1, 9, 16), 'P': MFMA_POINTS, 'd': (1, 5, 24, 25, 52, 53, D_MAX)}
+MFMA_PARTNERS = {'mode': ('path', 'point'), 'ngrad': ('0', '1', 'N'), 'max_blocks': (1, 0), 'table': (True, False)}
+MFMA_PAIRS = (('W', 'P'), ('q', 'P'), ('P', 'd'))
+
+
+def _no_table_in_point_mode(rnd, c):
+    """the x-projection table exists per path: a point-mode candidate with a table gives up one of the two"""
+    if c['table'] and c['mode'] == 'point':
+        if rnd.random() < 0.5:
+            c['mode'] = 'path'
+        else:
+            c['table'] = False
+
+
+MFMA_CASES = cover(MFMA_AXES, MFMA_PARTNERS, MFMA_PAIRS, fixed=_no_table_in_point_mode, seed=23)
+assert not missing(MFMA_CASES, MFMA_AXES, MFMA_PARTNERS, MFMA_PAIRS)
+assert 40 <= len(MFMA_CASES) <= 80, len(MFMA_CASES)
+
+
+def _mid(c):
+    return 'W%d-q%d-P%dx%d-d%d-%s-ngrad%s-cap%d%s' % (c['W'], c['q'], c['P'][0], c['P'][1], c['d'], c['mode'], c['ngrad'], c['max_blocks'],
+                                                      '-table' if c['table'] else '')
+
+
+@pytest.mark.parametrize('c', MFMA_CASES, ids=_mid)
+def test_testnet_containers_50_64_under_guards(c):
+    """the kernels of the flagship workload at the edge shapes: the input layer entirely or in part from LDS (d = 24 | 25, 52 | 53),
+    from the x-projection table, one block taking every tile (max_blocks = 1: tickets from 65 points on) against the default cap"""
+    _run_testnet(c['W'], c['q'], c['d'], c['mode'], c['P'], c['ngrad'], 'mfma', 960 + MFMA_CASES.index(c), c['max_blocks'], c['table'])
 
 
 # ---- the oracle's own rounding spread (CPU) ------------------------------------------------------------------------------------------
