@@ -298,8 +298,10 @@ int xw_disc_tiled_bwd(const double* xT, const double* t, const double* tpp, cons
  * xw_weak_partials ADDS this rank's partial sums into scal[0..2] (and [7..8]); zero scal first; all-reduce scal[0..8]
  * across ranks.
  *   The grid-wide sums are deterministic (per-block partials + last-block final sum, no float atomics): `work` is a
- *   caller-provided scratch of xw_reduce_work_size() doubles, zero-initialised ONCE (the kernels leave it clean), not
- *   shared between launches that may run concurrently.
+ *   caller-provided scratch of xw_reduce_work_size() doubles, zero-initialised ONCE: it then serves any sequence of
+ *   launches of xw_weak_partials / xw_bdry_partials, of any sizes and in any order (the ticket word has a fixed place behind
+ *   the partial sums of the largest launch and is reset by every launch; the partial sums themselves are left behind and are
+ *   never read before they are rewritten).  It must not be shared between launches that may run concurrently.
  *   w: distance-to-boundary weight, per path (w_per_point=0, [N]) or per point ([L,N]);  wt: d w/dt [L,N] or NULL (=0)
  *   s3x[N]: the l=0 gradient-contraction term  sum_ij a_ij d_i phi d_j u + sum_i b_i phi d_i u  (src/loss.py:66-69);
  *           NULL for a = identity, b = 0: then it is contracted in-kernel from gx[d,N], gs[N] (xw_ode_bwd), ghT[d,N]

@@ -793,6 +793,8 @@ def test_adam_matches_torch_formula():
         KN.adam(pc, slabs.cuda(), m, v, step, 0.015, gextraA=extra.cuda(), gslabB=slabsB.cuda(), scal=scal.cuda())
     assert int(step.item()) == 3
     _close(pc, p['p'], 1e-13, 'adam')
+    _close(m, state['m_p'], 1e-13, 'adam m')
+    _close(v, state['v_p'], 1e-13, 'adam v')
 
 
 def test_dims_outside_the_compiled_set_fail_loudly():

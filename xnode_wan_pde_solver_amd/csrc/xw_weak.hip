@@ -20,10 +20,15 @@ __device__ __forceinline__ double wave_sum(double x) { return xw_sum_over_g(xw_s
 // Deterministic grid-wide sum of NV per-thread partials: every block stores its partial sums to `work`, the block that
 // arrives last (agent-scope ticket) adds them up in block order and accumulates into dst[0..NV).  Float atomics would
 // be shorter but make two runs of the same step differ in the last bits; training must be bit-reproducible
-// (checkpoint/resume, test_test_net_reuse_is_exact).  work: NV * gridDim.x doubles + 1 ticket word (kept at zero
-// between launches: the last block resets it).  Hand-off follows cdna_hip_programming.md Guideline 16: stores ->
+// (checkpoint/resume, test_test_net_reuse_is_exact).  work: NV * gridDim.x doubles of partials from work[0] on, and the ticket word
+// at the FIXED index XW_REDUCE_TICKET behind the largest launch's partials (6 values x 1024 blocks, the cap of XW_REDUCE_BLOCKS): the
+// last block resets it, and no partial of any launch shape can land on it -- so one zero-initialised `work` serves any sequence of
+// non-concurrent launches, whatever their grid sizes and NV (a ticket at work[gridDim.x * NV] sat on a stale partial of an
+// earlier, larger launch: t == gridDim.x - 1 then never held and dst was silently left as it was).
+// Hand-off follows cdna_hip_programming.md Guideline 16: stores ->
 // s_waitcnt vmcnt(0) -> barrier -> lane-0 release fence -> ticket; consumer: ticket -> acquire fence -> barrier -> loads.
 // NV > 3: values 3, 4 go to dst[7], dst[8] (scal[4..6] are the loss values), value 5 to dst[3] (the boundary sum of squares)
+#define XW_REDUCE_TICKET (6 * 1024)
 template <int NV>
 __device__ __forceinline__ bool grid_sum(double (&val)[NV], double* __restrict__ work, double* __restrict__ dst) {
   __shared__ double red[NV][16];                        // (blocks of up to 16 waves)
@@ -42,7 +47,7 @@ __device__ __forceinline__ bool grid_sum(double (&val)[NV], double* __restrict__
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  unsigned int* ticket = reinterpret_cast<unsigned int*>(work + (long)gridDim.x * NV);
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(work + XW_REDUCE_TICKET);
   if (threadIdx.x == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -587,7 +592,7 @@ extern "C" int xw_slab_sum(const double* gslab, int nslab, int P, int accumulate
 }
 
 extern "C" int xw_abi_version(void) { return 33; }
-extern "C" int xw_reduce_work_size(void) { return 6 * 1024 + 8; }
+extern "C" int xw_reduce_work_size(void) { return XW_REDUCE_TICKET + 8; }   // partials | ticket word + 7 spare doubles
 
 extern "C" int xw_supported_dims(char* buf, int buflen) {
   static const char s[] = "ode (H,K)=(20,10),(32,12),(64,16), m=1..10 [MFMA]; any other H<=64, K<=16, m<=32 [generic path: vector ALU, slow]; disc_fwd W=50,64,96,128 any q; disc_bwd W=50 (q=9 unrolled, any q from the record), W=64,96,128 (from the record) [MFMA]; any other W<=128, q<=16 [generic path, from the record]; disc W<=256, q<=32 beyond those [tiled MFMA family, from the record]; d<=126";
