@@ -177,6 +177,47 @@ def test_every_cotangent_form(L):
     _check_grads(None, None, KN.slab_sum(sa).cpu(), _grads(ua, la, ubar, retain=False), 1e-10, 'parameters only')
 
 
+@pytest.mark.parametrize('L', [2, 3])
+@pytest.mark.parametrize('N', [17, 1])
+@pytest.mark.parametrize('d,H,K,m', [(2, 5, 3, 1), (4, 33, 17, 2)])
+def test_startup_steps_are_the_rk4_stepper_to_the_bit(d, H, K, m, N, L):
+    """With two or three sample times 'explicit_adams' consists of rk4 start-up steps only (no history term reaches a step: fbar
+    is an exact zero).  The forward passes run the same step function; the sweeps hold two texts of the rk4 reverse and the tail
+    (kt_ode_bwd's own, and the shared ones of csrc/xw_tiled_blocks.h), which this test pins to each other: u, Y and the sweep's
+    gx, gs, gslab are the rk4 stepper's bits -- x only, parameters only, both.  N = 17: a full tile and a tile of one path;
+    (4, 33, 17, 2) crosses the padding to 16 rows and 4 columns."""
+    from xnode_wan_pde_solver_amd import kernels as KN
+    dev = torch.device('cuda')
+    _, blob = _theta(H, K, m, d, 40 + H)
+    bc, P = blob.to(dev), blob.numel()
+    x, t, start, ubar = _sample(N, L, d, 50 + N + L)
+    tc, ub = t.to(dev), ubar.t().contiguous().to(dev)
+
+    def fwd_job():
+        return dict(xT=x.t().contiguous().to(dev), start=start.to(dev), u=torch.full((L, N), float('nan'), dtype=F64, device=dev),
+                    Y=torch.full((L, H, N), float('nan'), dtype=F64, device=dev))
+
+    rk, ab = fwd_job(), fwd_job()
+    KN.tiled_ode_fwd_multi([rk], tc, bc, KN.METHODS['rk4'], H, K, m)
+    KN.adams_tiled_fwd_multi([ab], tc, bc, H, K, m)
+    assert torch.isfinite(rk['Y']).all()
+    assert torch.equal(ab['u'], rk['u']) and torch.equal(ab['Y'], rk['Y'])
+    for want_x, want_params in ((True, False), (False, True), (True, True)):
+        outs = []
+        for sweep in (lambda jobs, **kw: KN.tiled_ode_bwd_multi(jobs, tc, bc, KN.METHODS['rk4'], H, K, m, **kw),
+                      lambda jobs, **kw: KN.adams_tiled_bwd_multi(jobs, tc, bc, H, K, m, **kw)):
+            o = dict(rk, ubar=ub)
+            if want_x:
+                o.update(gx=torch.full((d, N), float('nan'), dtype=F64, device=dev), gs=torch.full((N,), float('nan'), dtype=F64, device=dev))
+            if want_params:
+                o.update(gslab=torch.full((KN.ode_bwd_slabs(N), P), float('nan'), dtype=F64, device=dev))
+            sweep([o], want_x=want_x, want_params=want_params)
+            outs.append(o)
+        for k in (('gx', 'gs') if want_x else ()) + (('gslab',) if want_params else ()):
+            assert torch.isfinite(outs[0][k]).all(), k
+            assert torch.equal(outs[1][k], outs[0][k]), '%s (want_x %s, want_params %s)' % (k, want_x, want_params)
+
+
 def test_results_are_bitwise_reproducible_and_graph_replayable():
     from xnode_wan_pde_solver_amd import kernels as KN
     H, K, m, d, L, N = 64, 16, 5, 7, 13, 500

@@ -3,7 +3,7 @@
 // pipe at the network's own runtime widths, u_hidden_dim H <= 256, u_hidden_hidden_dim K <= 256, u_layers 1..32.
 //
 // One 64-lane wave = one workgroup = one tile of 16 paths; every layer of the field is a product on v_mfma_f64_16x16x4 written with
-// the building blocks of xw_tiled_blocks.h (tgemm / touter / trowsum / tfield / tfield_vjp / tile_x / tlift / tcomb).  The tile's
+// the building blocks of xw_tiled_blocks.h (tgemm / touter / trowsum / tfield / tfield_vjp / tile_x / tlift / tcomb / tload / tstore).  The tile's
 // vectors are [rows][16] doubles in a per-tile slice of a caller-provided workspace (xw_tdopri5_work: the family's TileWork, and
 // behind it the stages k_0 .. k_6 -- in the sweep also their cotangents); phases are ordered by sync_tile().  The workspace is per
 // LAUNCH: nothing in it is read by a later launch.  In particular xproj = Win[:, 0..d) x + Win.b is recomputed by every launch
@@ -24,13 +24,13 @@
 //   kq_init1    y0 = lift(start), f0 = F(t0, y0); record slot 0, output l = 0; d0 = ||y0/scale||, d1 = ||f0/scale||, h0
 //   kq_init2    d2 = ||(F(t0 + h0, y0 + h0 f0) - f0)/scale|| / h0; the first step; the controller starts
 //   kq_attempt  one attempted step of every job that is not done (the host enqueues them in chunks)
-//   kq_sweep    the reverse of the ACCEPTED steps, step sizes as constants; the tail (l = 0, the lift, the x side) is kt_ode_bwd's
+//   kq_sweep    the reverse of the ACCEPTED steps, step sizes as constants; prologue and tail are the family's (sweep_prologue, sweep_tail)
 #include "xw_common.h"
 #include "xnwan.h"
 
 namespace {
-#include "xw_tiled_blocks.h"
 #include "xw_generic_cot.h"
+#include "xw_tiled_blocks.h"
 
 __device__ __forceinline__ double gsum64(double x) { return xw_sum_over_g(xw_sum_over_n(x)); }   // sum over the wave
 
@@ -47,31 +47,6 @@ __host__ __device__ inline TdWork td_work(int sweep, int d, int H, int K, int m)
   q.k = q.w.total;
   q.total = q.w.total + 16L * H * (sweep ? 14 : 7);
   return q;
-}
-
-// v[h][c] = src[h][p0 + c] of an [H][N] array, clamped to the last path (the caller orders it with sync_tile)
-__device__ __forceinline__ void tload(int H, int N, int p0, const double* __restrict__ src, double* v) {
-  for (int e = lane_id(); e < 16 * H; e += 64) {
-    const int p = p0 + (e & 15);
-    v[e] = src[(long)(e >> 4) * N + (p < N ? p : N - 1)];
-  }
-}
-// the reverse, for the paths the job has
-__device__ __forceinline__ void tstore(int H, int N, int p0, const double* v, double* __restrict__ dst) {
-  for (int e = lane_id(); e < 16 * H; e += 64)
-    if (p0 + (e & 15) < N) dst[(long)(e >> 4) * N + p0 + (e & 15)] = v[e];
-}
-
-// u[l] = FL(y) and Y[l] = y for the tile (y complete: behind a sync_tile)
-__device__ void tput_output(const XwDopriJob& j, const Net& n, int l, int p0, const double* y) {
-  const int l16 = lane_id() & 15, N = j.N, H = n.H;
-  if (lane_id() < 16 && p0 + l16 < N) {
-    const double* flw = n.th + n.o.FLw;
-    double u = n.th[n.o.FLb];
-    for (int h = 0; h < H; ++h) u = fma(flw[h], y[h * 16 + l16], u);
-    j.u[(long)l * N + p0 + l16] = u;
-  }
-  if (j.Y) tstore(H, N, p0, y, j.Y + (long)l * H * N);
 }
 
 // a = y + dt sum_{q < st} a_{st,q} k_q: the input of stage st (st = 0: y itself)
@@ -115,7 +90,7 @@ __global__ void __launch_bounds__(64) kq_init1(const Jobs<XwDopriJob> J, const d
   tstore(H, N, p0, y, j.rec_y);
   tstore(H, N, p0, f, j.fbuf);
   for (int l = 0; l < L; ++l)                               // t_0 (and sample times that do not lie past it) give y0 itself
-    if (l == 0 || !(tf[l] > tf[0])) tput_output(j, n, l, p0, y);
+    if (l == 0 || !(tf[l] > tf[0])) tput_output(n, j.u, j.Y, l, N, p0, y);
   if (job_sum<2>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) {
     const double cnt = (double)N * Hn;
     const double d0 = sqrt(acc[0] / cnt), d1 = sqrt(acc[1] / cnt);
@@ -227,7 +202,7 @@ __global__ void __launch_bounds__(64) kq_attempt(const Jobs<XwDopriJob> J, const
       pv[e] = y0[e] + s_;
     }
     sync_tile();
-    tput_output(j, n, l, p0, pv);
+    tput_output(n, j.u, j.Y, l, N, p0, pv);
     sync_tile();
   }
   if (!job_sum<1>(acc, j.work, c, nb, lb) || threadIdx.x != 0) return;
@@ -274,16 +249,6 @@ __global__ void __launch_bounds__(64) kq_attempt(const Jobs<XwDopriJob> J, const
   }
 }
 
-// slab's read-out entries for the output state v under the cotangent ub (both complete: behind a sync_tile)
-__device__ void readout_grad(double* slab, const Net& n, const double* v, const double* ub) {
-  trowsum(slab, n.o.FLw, 1, n.H, v, ub, 1.0);
-  if (lane_id() == 0) {
-    double s = 0.0;
-    for (int p = 0; p < 16; ++p) s += ub[p];
-    slab[n.o.FLb] += s;
-  }
-}
-
 // Reverse of the accepted steps (step sizes and grid constants), per tile: kd_sweep of xw_dopri.hip on tiles.  Step s:
 // y_{s+1} = y_s + dt sum_j b_j k_j, stage j at (t_s + c_j dt, y_s + dt sum_{q<j} a_jq k_q); the outputs the step covers are
 // p(x_i) = y_s + dt sum_j w_j(x_i) k_j.  The stages are recomputed from the recorded y_s, their VJPs taken in reverse order.
@@ -296,7 +261,6 @@ __global__ void __launch_bounds__(64) kq_sweep(const Jobs<XwDopriSweepJob> J, co
   const XwDopriSweepJob& sj = J.j[job_of(J, lb)];
   const XwOdeBwdJob& job = sj.b;
   const int N = job.N, p0 = lb * 16;
-  const bool want_x = (mode & 1) != 0, ones_x = (mode & 4) != 0;
   double* slab = (mode & 2) ? job.gslab + (long)lb * u_offsets(d, H, K).total : nullptr;
   const Net n = {theta, u_offsets(d, H, K), d, H, K, m};
   const TdWork q = td_work(1, d, H, K, m);
@@ -317,14 +281,8 @@ __global__ void __launch_bounds__(64) kq_sweep(const Jobs<XwDopriSweepJob> J, co
   double* kk = ws + q.k;
   double* kb = kk + 16L * H * 7;
   double* ub = ws + w.ub;
-  double* st = ws + w.st;
-  double* Sx = ws + w.total - 16L * K;
-  const int l16 = lane_id() & 15;
-  const bool lane_active = p0 + l16 < N;
-  if (lane_id() < 16) st[l16] = job.start[lane_active ? p0 + l16 : N - 1];
-  for (int e = lane_id(); e < 16 * K; e += 64) Sx[e] = 0.0;
-  for (int e = lane_id(); e < 16 * H; e += 64) lam[e] = carry[e] = 0.0;
-  tile_x(n, w, ws, job.xT, N, p0);
+  for (int e = lane_id(); e < 16 * H; e += 64) carry[e] = 0.0;
+  sweep_prologue(n, w, ws, job, p0, lam);
   const double* flw = theta + n.o.FLw;
   const int na = (int)sj.ctl[C_NACC];
   int l = L - 1;                                               // the next output to reverse (descending)
@@ -343,7 +301,7 @@ __global__ void __launch_bounds__(64) kq_sweep(const Jobs<XwDopriSweepJob> J, co
       kb[16L * H * 6 + e] += carry[e];
     }
     for (; l >= 1 && tf[l] > t0; --l) {
-      if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, l, L, p0 + l16) : 0.0;
+      tcot_ub(job, l, L, p0, ub);
       double dw[7];
       dense_weights((tf[l] - t0) / (t1 - t0), dw);
       if (slab)
@@ -379,52 +337,10 @@ __global__ void __launch_bounds__(64) kq_sweep(const Jobs<XwDopriSweepJob> J, co
   }
   // sample times that do not lie past t_0 read y0 itself
   for (; l >= 1; --l) {
-    if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, l, L, p0 + l16) : 0.0;
     if (slab) tload(H, N, p0, sj.rec_y, a);
-    sync_tile();
-    if (slab) readout_grad(slab, n, a, ub);
-    for (int e = lane_id(); e < 16 * H; e += 64) lam[e] = fma(flw[e >> 4], ub[e & 15], lam[e]);
-    sync_tile();
+    tcot_output(job, n, l, L, p0, ub, a, lam, slab);
   }
-  // l = 0: read-out, then the lift 1 -> H -> H -> H; with mode bit 2 the x-side outputs are those of the ALL-ONES cotangent
-  // while the parameter gradients use the job's own (the tail of kt_ode_bwd, xw_tiled.hip)
-  if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, 0, L, p0 + l16) : 0.0;
-  sync_tile();
-  tlift(n, st, p0v, p2v, y0);
-  if (slab) readout_grad(slab, n, y0, ub);
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 0 && !slab) continue;
-    if (pass == 1 && !(want_x && job.gs != nullptr)) continue;
-    const bool ones = pass == 1 && ones_x;
-    for (int e = lane_id(); e < 16 * H; e += 64) l0[e] = fma(flw[e >> 4], ones ? 1.0 : ub[e & 15], lam[e]);
-    sync_tile();
-    tgemm(theta + n.o.IL4w, 1, H, H, H, l0, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p2v, dh2);
-    tgemm(theta + n.o.IL2w, 1, H, H, H, dh2, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p0v, dh1);
-    if (pass == 0) {
-      touter(slab, n.o.IL4w, H, H, H, l0, p2v, A_RELU);
-      touter(slab, n.o.IL2w, H, H, H, dh2, p0v, A_RELU);
-      trowsum(slab, n.o.IL4b, 1, H, l0, nullptr, 1.0);
-      trowsum(slab, n.o.IL2b, 1, H, dh2, nullptr, 1.0);
-      trowsum(slab, n.o.IL0w, 1, H, dh1, st, 1.0);
-      trowsum(slab, n.o.IL0b, 1, H, dh1, nullptr, 1.0);
-      sync_tile();
-    } else if (lane_id() < 16 && lane_active) {
-      double s = 0.0;
-      for (int i = 0; i < H; ++i) s = fma(theta[n.o.IL0w + i], dh1[i * 16 + l16], s);
-      job.gs[p0 + l16] = s;
-    }
-  }
-  // the x columns and the bias of the input layer, from the summed cotangent of its pre-activation
-  if (slab) {
-    trowsum(slab, n.o.Winb, 1, K, Sx, nullptr, 1.0);
-    touter(slab, n.o.Win, n.o.ldin, K, d, Sx, ws + w.xt, A_PLAIN);
-  }
-  if (want_x && job.gx != nullptr) {
-    double* gxt = ws + w.xt + 16L * d;
-    tgemm(theta + n.o.Win, 1, n.o.ldin, d, K, Sx, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gxt);
-    for (int e = lane_id(); e < 16 * d; e += 64)
-      if (p0 + (e & 15) < N) job.gx[(long)(e >> 4) * N + p0 + (e & 15)] = gxt[e];
-  }
+  sweep_tail(n, w, ws, job, L, p0, mode, slab, lam, p0v, p2v, y0, l0, dh2, dh1);
 }
 
 bool dims_ok(int d, int H, int K, int m) { return xw_tiled_ode_ok(d, H, K, m) != 0; }   // the family's widths and depths
@@ -500,10 +416,7 @@ extern "C" int xw_tdopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const do
   const long Pu = u_offsets(d, H, K).total;
   for (int i = 0; i < njobs; ++i) {
     const XwDopriSweepJob& j = jobs[i];
-    if (!j.b.xT || !j.b.start || !j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || j.b.N < 1) return XW_E_ARG;
-    if (!cot_job_ok(j.b)) return XW_E_ARG;
-    if ((mode & 2) && !j.b.gslab) return XW_E_ARG;
-    if ((mode & 1) && !(mode & 4) && (!j.b.gx || !j.b.gs)) return XW_E_ARG;
+    if (!j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || !sweep_job_ok(j.b, mode)) return XW_E_ARG;
     P.blk0[i + 1] = P.blk0[i] + (j.b.N + 15) / 16;
   }
   if (mode & 2)

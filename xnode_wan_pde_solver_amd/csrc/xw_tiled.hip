@@ -23,6 +23,7 @@
 #include "xnwan.h"
 
 namespace {
+#include "xw_generic_cot.h"
 #include "xw_tiled_blocks.h"
 
 // ---- solver 'explicit_adams' (torchdiffeq fixed_adams.py AdamsBashforth): the history of field values ----------------------
@@ -79,49 +80,15 @@ __global__ void __launch_bounds__(64) kt_ode_fwd(XwOdeFwdJob job, const double* 
   if (lane_id() < 16) st[l16] = job.start[p0 + l16 < N ? p0 + l16 : N - 1];
   tile_x(n, w, ws, job.xT, N, p0);
   tlift(n, st, acc, cc, y);
-  const double* flw = theta + n.o.FLw;
   for (int l = 0; l < L; ++l) {
-    if (l > 0) {
-      const double t0 = tf[l - 1], dt = tf[l] - tf[l - 1];
-      if (method == 0) {
-        tfield(n, w, ws, t0, y, fo, false);
-        tcomb(H, y, y, dt, fo);
-      } else if (method == 1) {
-        tfield(n, w, ws, t0, y, fo, false);
-        tcomb(H, tmp, y, dt / 2, fo);
-        tfield(n, w, ws, t0 + dt / 2, tmp, fo, false);
-        tcomb(H, y, y, dt, fo);
-      } else {                                                   // 3/8 rule: acc = k1 + 3 k2 + 3 k3 + k4, cc = k1 - k2
-        tfield(n, w, ws, t0, y, fo, false);
-        tcomb(H, acc, nullptr, 1.0, fo);
-        tcomb(H, cc, nullptr, 1.0, fo);
-        tcomb(H, tmp, y, dt / 3, fo);
-        tfield(n, w, ws, t0 + dt / 3, tmp, fo, false);
-        tcomb(H, acc, acc, 3.0, fo);
-        tcomb(H, tmp, y, dt, fo, -dt / 3, cc);
-        tcomb(H, cc, cc, -1.0, fo);
-        tfield(n, w, ws, t0 + 2 * dt / 3, tmp, fo, false);
-        tcomb(H, acc, acc, 3.0, fo);
-        tcomb(H, tmp, y, dt, cc, dt, fo);
-        tfield(n, w, ws, t0 + dt, tmp, fo, false);
-        tcomb(H, acc, acc, 1.0, fo);
-        tcomb(H, y, y, dt / 8, acc);
-      }
-    }
-    if (lane_id() < 16 && p0 + l16 < N) {
-      double u = theta[n.o.FLb];
-      for (int j = 0; j < H; ++j) u = fma(flw[j], y[j * 16 + l16], u);
-      job.u[(long)l * N + p0 + l16] = u;
-    }
-    if (job.Y)
-      for (int e = lane_id(); e < 16 * H; e += 64)
-        if (p0 + (e & 15) < N) job.Y[((long)l * H + (e >> 4)) * N + p0 + (e & 15)] = y[e];
+    if (l > 0) tstep_fwd(n, w, ws, method, tf[l - 1], tf[l] - tf[l - 1], y, acc, cc, tmp, fo);
+    tput_output(n, job.u, job.Y, l, N, p0, y);
   }
 }
 
 // the explicit_adams forward pass: kt_ode_fwd with the field values f_n kept in a ring of XWA_HIST H-vectors behind the tile's
-// TileWork (slot n % XWA_HIST); step n >= 2 is one field evaluation and the Adams-Bashforth sum, steps 0 and 1 are kt_ode_fwd's
-// rk4 stages with k1 = f_n
+// TileWork (slot n % XWA_HIST); step n >= 2 is one field evaluation and the Adams-Bashforth sum, steps 0 and 1 are the rk4 step
+// of kt_ode_fwd (tstep_rk4) from k1 = f_n
 __global__ void __launch_bounds__(64) kt_adams_fwd(XwOdeFwdJob job, const double* __restrict__ tf, const double* __restrict__ theta,
                                                    int L, int d, int H, int K, int m, double* __restrict__ work) {
   set_prio(job.prio_drop);
@@ -140,7 +107,6 @@ __global__ void __launch_bounds__(64) kt_adams_fwd(XwOdeFwdJob job, const double
   if (lane_id() < 16) st[l16] = job.start[p0 + l16 < N ? p0 + l16 : N - 1];
   tile_x(n, w, ws, job.xT, N, p0);
   tlift(n, st, acc, cc, y);
-  const double* flw = theta + n.o.FLw;
   for (int l = 0; l < L; ++l) {
     if (l > 0) {
       const int s = l - 1;                                       // the step y_s -> y_l
@@ -155,35 +121,19 @@ __global__ void __launch_bounds__(64) kt_adams_fwd(XwOdeFwdJob job, const double
           y[e] += dy;
         }
         sync_tile();
-      } else {                                                   // rk4 start-up step, 3/8 rule (kt_ode_fwd, method 2)
-        tcomb(H, acc, nullptr, 1.0, k1);
-        tcomb(H, cc, nullptr, 1.0, k1);
-        tcomb(H, tmp, y, dt / 3, k1);
-        tfield(n, w, ws, t0 + dt / 3, tmp, fo, false);
-        tcomb(H, acc, acc, 3.0, fo);
-        tcomb(H, tmp, y, dt, fo, -dt / 3, cc);
-        tcomb(H, cc, cc, -1.0, fo);
-        tfield(n, w, ws, t0 + 2 * dt / 3, tmp, fo, false);
-        tcomb(H, acc, acc, 3.0, fo);
-        tcomb(H, tmp, y, dt, cc, dt, fo);
-        tfield(n, w, ws, t0 + dt, tmp, fo, false);
-        tcomb(H, acc, acc, 1.0, fo);
-        tcomb(H, y, y, dt / 8, acc);
+      } else {                                                   // rk4 start-up step from k1 = f_s
+        tstep_rk4(n, w, ws, t0, dt, y, k1, acc, cc, tmp, fo);
       }
     }
-    if (lane_id() < 16 && p0 + l16 < N) {
-      double u = theta[n.o.FLb];
-      for (int j = 0; j < H; ++j) u = fma(flw[j], y[j * 16 + l16], u);
-      job.u[(long)l * N + p0 + l16] = u;
-    }
-    if (job.Y)
-      for (int e = lane_id(); e < 16 * H; e += 64)
-        if (p0 + (e & 15) < N) job.Y[((long)l * H + (e >> 4)) * N + p0 + (e & 15)] = y[e];
+    tput_output(n, job.u, job.Y, l, N, p0, y);
   }
 }
 
-#include "xw_generic_cot.h"
-
+// The fixed-grid sweep keeps its own text -- step reverses, cotangent block and tail written out, none of the shared sweep pieces of
+// xw_tiled_blocks.h (tstep_rk4_bwd, tcot_output, sweep_prologue, sweep_tail), which kt_adams_bwd and the dopri5 sweep use: with any
+// of them inlined here the compiler lays this kernel and the out-of-line blocks out differently and midpoint's sweep at (20, 10, 8)
+// measured 6 to 11 % slower (profiles/r18_tiled_shared_blocks.md).  A change to the tail or to the rk4 reverse lands here AND there;
+// tests/test_gpu_adams.py pins the two to the same bits.
 __global__ void __launch_bounds__(64) kt_ode_bwd(XwOdeBwdJob job, const double* __restrict__ tf, const double* __restrict__ theta,
                                                   int method, int L, int d, int H, int K, int m, int mode, double* __restrict__ work) {
   set_prio(mode >> 5);
@@ -272,7 +222,7 @@ __global__ void __launch_bounds__(64) kt_ode_bwd(XwOdeBwdJob job, const double* 
     }
   }
   // l = 0: read-out, then the lift 1 -> H -> H -> H; with mode bit 2 the x-side outputs are those of the ALL-ONES cotangent
-  // while the parameter gradients use the job's own (xw_generic.hip kg_ode_bwd)
+  // while the parameter gradients use the job's own (xw_generic.hip kg_ode_bwd) -- sweep_tail's text
   if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, 0, L, p0 + l16) : 0.0;
   sync_tile();
   double* p0v = Y2;
@@ -330,63 +280,25 @@ __global__ void __launch_bounds__(64) kt_ode_bwd(XwOdeBwdJob job, const double* 
 //   fbar_k = sum_{n = max(k, 2)}^{min(k + XWA_HIST - 1, L - 2)} dt_n beta[ord_n][n - k] ybar_{n+1}      (dt_n constants);
 // then ybar_k = ybar_{k+1} + J_F(t_k, y_k)^T fbar_k (+ the cotangent on u at k) for k >= 2, with the field's activations recomputed
 // from Y[k].  The start-up steps k = 0, 1 take the rk4 reverse with fbar_k added to the cotangent of k1 (the same evaluation as
-// the history entry).  The cotangent at l = 0, the lift and the x-side outputs are kt_ode_bwd's.
+// the history entry): tstep_rk4_bwd with fbar_k as the further cotangent on k1.
 __global__ void __launch_bounds__(64) kt_adams_bwd(XwOdeBwdJob job, const double* __restrict__ tf, const double* __restrict__ theta,
                                                    int L, int d, int H, int K, int m, int mode, double* __restrict__ work) {
   set_prio(mode >> 5);
   const int N = job.N, p0 = blockIdx.x * 16;
-  const bool want_x = (mode & 1) != 0, ones_x = (mode & 4) != 0;
   double* slab = (mode & 2) ? job.gslab + (long)blockIdx.x * u_offsets(d, H, K).total : nullptr;
   const Net n = {theta, u_offsets(d, H, K), d, H, K, m};
   const TileWork w = tile_work(1, d, H, K, m);
   double* ws = work + (long)blockIdx.x * (w.total + 16L * H * (XWA_HIST + 1));
-  double* hv = ws + w.hv;
-  double* lam = hv;
-  double* Y1 = hv + 16L * H * 1;
-  double* Y2 = hv + 16L * H * 2;
-  double* Y3 = hv + 16L * H * 3;
-  double* Y4 = hv + 16L * H * 4;
-  double* cc = hv + 16L * H * 5;
-  double* fo = hv + 16L * H * 6;
-  double* g4 = hv + 16L * H * 7;
-  double* g3 = hv + 16L * H * 8;
-  double* g2 = hv + 16L * H * 9;
-  double* a = hv + 16L * H * 10;
-  double* gy = hv + 16L * H * 11;
+  const SweepVecs v = sweep_vecs(ws + w.hv, H);
   double* ring = ws + w.total;
   double* fb = ring + 16L * H * XWA_HIST;
-  double* ub = ws + w.ub;
-  double* st = ws + w.st;
-  double* Sx = ws + w.total - 16L * K;
-  const int l16 = lane_id() & 15;
-  const bool lane_active = p0 + l16 < N;
-  if (lane_id() < 16) st[l16] = job.start[lane_active ? p0 + l16 : N - 1];
-  for (int e = lane_id(); e < 16 * K; e += 64) Sx[e] = 0.0;
-  for (int e = lane_id(); e < 16 * H; e += 64) lam[e] = 0.0;
-  tile_x(n, w, ws, job.xT, N, p0);
-  const double* flw = theta + n.o.FLw;
+  sweep_prologue(n, w, ws, job, p0, v.lam);
   for (int l = L - 1; l >= 1; --l) {
-    if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, l, L, p0 + l16) : 0.0;
-    for (int e = lane_id(); e < 16 * H; e += 64) {
-      const int p = p0 + (e & 15);
-      Y1[e] = job.Y[((long)(l - 1) * H + (e >> 4)) * N + (p < N ? p : N - 1)];
-      Y2[e] = job.Y[((long)l * H + (e >> 4)) * N + (p < N ? p : N - 1)];
-    }
-    sync_tile();
+    tload(H, N, p0, job.Y + (long)(l - 1) * H * N, v.Y1);
+    tload(H, N, p0, job.Y + (long)l * H * N, v.Y2);
+    tcot_output(job, n, l, L, p0, ws + w.ub, v.Y2, v.lam, slab);
     double* rl = ring + 16L * H * (l % XWA_HIST);
-    for (int e = lane_id(); e < 16 * H; e += 64) {
-      lam[e] = fma(flw[e >> 4], ub[e & 15], lam[e]);
-      rl[e] = lam[e];                                              // ybar_l is complete: into the ring
-    }
-    if (slab) {
-      trowsum(slab, n.o.FLw, 1, H, Y2, ub, 1.0);
-      if (lane_id() == 0) {
-        double s = 0.0;
-        for (int p = 0; p < 16; ++p) s += ub[p];
-        slab[n.o.FLb] += s;
-      }
-    }
-    sync_tile();
+    for (int e = lane_id(); e < 16 * H; e += 64) rl[e] = v.lam[e];   // ybar_l is complete: into the ring
     const int k = l - 1;
     const double t0 = tf[k], dt = tf[l] - tf[k];
     const int q0 = k > 2 ? k : 2, q1 = k + XWA_HIST - 1 < L - 2 ? k + XWA_HIST - 1 : L - 2;
@@ -397,83 +309,13 @@ __global__ void __launch_bounds__(64) kt_adams_bwd(XwOdeBwdJob job, const double
     }
     sync_tile();
     if (k >= 2) {                                                  // y_l = y_k + sum_j c_j f_{k-j}: lam becomes ybar_k
-      tfield_vjp(n, w, ws, t0, Y1, fb, gy, slab);
-      tcomb(H, lam, lam, 1.0, gy);
-      continue;
-    }
-    tfield(n, w, ws, t0, Y1, fo, true);                            // rk4 start-up step (kt_ode_bwd, method 2); k1 = f_k
-    tcomb(H, cc, nullptr, 1.0, fo);
-    tcomb(H, Y2, Y1, dt / 3, fo);
-    tfield(n, w, ws, t0 + dt / 3, Y2, fo, true);
-    tcomb(H, Y3, Y1, dt, fo, -dt / 3, cc);
-    tcomb(H, cc, cc, -1.0, fo);
-    tfield(n, w, ws, t0 + 2 * dt / 3, Y3, fo, true);
-    tcomb(H, Y4, Y1, dt, cc, dt, fo);
-    tcomb(H, a, nullptr, dt / 8, lam);
-    tfield_vjp(n, w, ws, t0 + dt, Y4, a, g4, slab);
-    tcomb(H, a, nullptr, 3 * dt / 8, lam, dt, g4);
-    tfield_vjp(n, w, ws, t0 + 2 * dt / 3, Y3, a, g3, slab);
-    tcomb(H, a, nullptr, 3 * dt / 8, lam, -dt, g4, dt, g3);
-    tfield_vjp(n, w, ws, t0 + dt / 3, Y2, a, g2, slab);
-    for (int e = lane_id(); e < 16 * H; e += 64)
-      a[e] = (dt / 8) * lam[e] + dt * g4[e] - (dt / 3) * g3[e] + (dt / 3) * g2[e] + fb[e];   // (+ fbar_k: k1 is f_k)
-    sync_tile();
-    tfield_vjp(n, w, ws, t0, Y1, a, gy, slab);
-    for (int e = lane_id(); e < 16 * H; e += 64) lam[e] += g4[e] + g3[e] + g2[e] + gy[e];
-    sync_tile();
-  }
-  // l = 0: read-out, then the lift 1 -> H -> H -> H; with mode bit 2 the x-side outputs are those of the ALL-ONES cotangent
-  // while the parameter gradients use the job's own (xw_generic.hip kg_ode_bwd)
-  if (lane_id() < 16) ub[l16] = lane_active ? cot_u(job, 0, L, p0 + l16) : 0.0;
-  sync_tile();
-  double* p0v = Y2;
-  double* p2v = Y3;
-  double* y0 = Y4;
-  double* l0 = cc;
-  double* dh2 = fo;
-  double* dh1 = g4;
-  tlift(n, st, p0v, p2v, y0);
-  if (slab) {
-    trowsum(slab, n.o.FLw, 1, H, y0, ub, 1.0);
-    if (lane_id() == 0) {
-      double s = 0.0;
-      for (int p = 0; p < 16; ++p) s += ub[p];
-      slab[n.o.FLb] += s;
+      tfield_vjp(n, w, ws, t0, v.Y1, fb, v.gy, slab);
+      tcomb(H, v.lam, v.lam, 1.0, v.gy);
+    } else {                                                       // rk4 start-up step; + fbar_k: k1 is f_k
+      tstep_rk4_bwd(n, w, ws, t0, dt, v, slab, fb);
     }
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 0 && !slab) continue;
-    if (pass == 1 && !(want_x && job.gs != nullptr)) continue;
-    const bool ones = pass == 1 && ones_x;
-    for (int e = lane_id(); e < 16 * H; e += 64) l0[e] = fma(flw[e >> 4], ones ? 1.0 : ub[e & 15], lam[e]);
-    sync_tile();
-    tgemm(theta + n.o.IL4w, 1, H, H, H, l0, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p2v, dh2);
-    tgemm(theta + n.o.IL2w, 1, H, H, H, dh2, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p0v, dh1);
-    if (pass == 0) {
-      touter(slab, n.o.IL4w, H, H, H, l0, p2v, A_RELU);
-      touter(slab, n.o.IL2w, H, H, H, dh2, p0v, A_RELU);
-      trowsum(slab, n.o.IL4b, 1, H, l0, nullptr, 1.0);
-      trowsum(slab, n.o.IL2b, 1, H, dh2, nullptr, 1.0);
-      trowsum(slab, n.o.IL0w, 1, H, dh1, st, 1.0);
-      trowsum(slab, n.o.IL0b, 1, H, dh1, nullptr, 1.0);
-      sync_tile();
-    } else if (lane_id() < 16 && lane_active) {
-      double s = 0.0;
-      for (int i = 0; i < H; ++i) s = fma(theta[n.o.IL0w + i], dh1[i * 16 + l16], s);
-      job.gs[p0 + l16] = s;
-    }
-  }
-  // the x columns and the bias of the input layer, from the summed cotangent of its pre-activation
-  if (slab) {
-    trowsum(slab, n.o.Winb, 1, K, Sx, nullptr, 1.0);
-    touter(slab, n.o.Win, n.o.ldin, K, d, Sx, ws + w.xt, A_PLAIN);
-  }
-  if (want_x && job.gx != nullptr) {
-    double* gxt = ws + w.xt + 16L * d;
-    tgemm(theta + n.o.Win, 1, n.o.ldin, d, K, Sx, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gxt);
-    for (int e = lane_id(); e < 16 * d; e += 64)
-      if (p0 + (e & 15) < N) job.gx[(long)(e >> 4) * N + p0 + (e & 15)] = gxt[e];
-  }
+  sweep_tail(n, w, ws, job, L, p0, mode, slab, v.lam, v.Y2, v.Y3, v.Y4, v.cc, v.fo, v.g4);
 }
 
 }  // namespace
@@ -534,13 +376,8 @@ static int tiled_bwd(bool ab, const XwOdeBwdJob* jobs, int njobs, const double* 
   if ((mode & 4) && (mode & 3) != 3) return XW_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   const long P = u_offsets(d, H, K).total;
-  for (int i = 0; i < njobs; ++i) {
-    const XwOdeBwdJob& j = jobs[i];
-    if (!j.xT || !j.start || !j.Y || j.N < 1) return XW_E_ARG;
-    if (!cot_job_ok(j)) return XW_E_ARG;
-    if ((mode & 2) && !j.gslab) return XW_E_ARG;
-    if ((mode & 1) && !(mode & 4) && (!j.gx || !j.gs)) return XW_E_ARG;
-  }
+  for (int i = 0; i < njobs; ++i)
+    if (!jobs[i].Y || !sweep_job_ok(jobs[i], mode)) return XW_E_ARG;
   const long per = tile_stride(ab, 1, d, H, K, m);
   long off = 0;
   for (int i = 0; i < njobs; ++i) {

@@ -1,6 +1,8 @@
-// xw_tiled_blocks.h -- the building blocks of the tiled stepper family (xw_tiled.hip): the per-tile workspace and the tile
-// products, field, VJP, lift and combinations that its kernels -- and the tiled dopri5 kernels of xw_tdopri.hip -- are written
-// with.  Library-internal; included INSIDE an anonymous namespace, after xw_common.h and xnwan.h.
+// xw_tiled_blocks.h -- the building blocks of the tiled stepper family: the per-tile workspace; the tile products, field, VJP, lift
+// and combinations; and the sequences its kernels share -- the fixed-grid step, the rk4 reverse, the output block, the cotangent on
+// u of a time index, the sweeps' prologue and tail, the host's check of a sweep job.  Used by xw_tiled.hip, xw_tiled_paths.hip and
+// xw_tdopri.hip; kt_ode_bwd alone keeps its own text of the sweep pieces (xw_tiled.hip says why).  Library-internal; included INSIDE an anonymous namespace, after xw_common.h, xnwan.h and
+// xw_generic_cot.h (cot_u, cot_job_ok).
 #pragma once
 
 #define XWT_MAX_H 256
@@ -209,18 +211,216 @@ __device__ void tcomb(int H, double* dst, const double* s0, double c1, const dou
   sync_tile();
 }
 
-// ---- per-path siblings (xw_tiled_paths.hip): every path of the tile on a time grid of its own ---------------------------------
-// The time t_p and the coefficients c*_p are PER LANE: the value of the lane's own path, column lane & 15.  tgemm's epilogue
-// (e = r * 16 + (lane & 15)) and tcomb's loop (e = lane + 64 i) touch columns e & 15 == lane & 15 only, so the originals, handed a
-// lane's own value, ARE the per-path forms: the same operations in the same order -- bias, fma(tcol[r], t_p, .), add;
-// fma(c_p, s1[e], v) -- and, on a tile whose 16 paths carry one grid, the same bits as with the scalar.  (tfield hands its time
-// to the time term of z_0's tgemm and nowhere else.)
-__device__ __forceinline__ void tfield_pp(const Net& n, const TileWork& w, double* ws, double t_p, const double* yin, double* fo) {
-  tfield(n, w, ws, t_p, yin, fo, false);
+// ---- tile <-> [rows][N] arrays -------------------------------------------------------------------------------------------------
+// v[h][c] = src[h][p0 + c] of an [H][N] array, clamped to the last path (the caller orders it with sync_tile)
+__device__ __forceinline__ void tload(int H, int N, int p0, const double* __restrict__ src, double* v) {
+  for (int e = lane_id(); e < 16 * H; e += 64) {
+    const int p = p0 + (e & 15);
+    v[e] = src[(long)(e >> 4) * N + (p < N ? p : N - 1)];
+  }
 }
-__device__ __forceinline__ void tcomb_pp(int H, double* dst, const double* s0, double c1_p, const double* s1, double c2_p = 0.0,
-                                         const double* s2 = nullptr, double c3_p = 0.0, const double* s3 = nullptr) {
-  tcomb(H, dst, s0, c1_p, s1, c2_p, s2, c3_p, s3);
+// the reverse, for the paths the job has
+__device__ __forceinline__ void tstore(int H, int N, int p0, const double* v, double* __restrict__ dst) {
+  for (int e = lane_id(); e < 16 * H; e += 64)
+    if (p0 + (e & 15) < N) dst[(long)(e >> 4) * N + p0 + (e & 15)] = v[e];
+}
+
+// u[row] = FL(y) and (Y not null) Y[row] = y for the tile (y complete: behind a sync_tile)
+__device__ __forceinline__ void tput_output(const Net& n, double* u, double* Y, long row, int N, int p0, const double* y) {
+  const int l16 = lane_id() & 15, H = n.H;
+  if (lane_id() < 16 && p0 + l16 < N) {
+    const double* flw = n.th + n.o.FLw;
+    double v = n.th[n.o.FLb];
+    for (int h = 0; h < H; ++h) v = fma(flw[h], y[h * 16 + l16], v);
+    u[row * N + p0 + l16] = v;
+  }
+  if (Y) tstore(H, N, p0, y, Y + row * H * N);
+}
+
+// ---- one step of the fixed-grid schemes (method 0 euler, 1 midpoint, 2 rk4 by the 3/8 rule) and its reverse ------------------
+// t0 and dt are passed BY VALUE: one grid for the tile (kt_ode_fwd: wave-uniform) or PER LANE -- the value of the lane's own path,
+// column lane & 15 (kt_ode_fwd_pp).  tgemm's epilogue (e = r * 16 + (lane & 15)) and tcomb's loop (e = lane + 64 i) touch columns
+// e & 15 == lane & 15 only, so the blocks, handed a lane's own value, ARE the per-path forms: the same operations in the same order
+// -- bias, fma(tcol[r], t_p, .), add; fma(c_p, s1[e], v) -- and, on a tile whose 16 paths carry one grid, the same bits as with the
+// scalar.  (tfield hands its time to the time term of z_0's tgemm and nowhere else.)
+
+// the rk4 step from an evaluated k1 = F(t0, y) (k1 may be fo): acc = k1 + 3 k2 + 3 k3 + k4, cc = k1 - k2
+__device__ __forceinline__ void tstep_rk4(const Net& n, const TileWork& w, double* ws, double t0, double dt, double* y, const double* k1,
+                                          double* acc, double* cc, double* tmp, double* fo) {
+  const int H = n.H;
+  tcomb(H, acc, nullptr, 1.0, k1);
+  tcomb(H, cc, nullptr, 1.0, k1);
+  tcomb(H, tmp, y, dt / 3, k1);
+  tfield(n, w, ws, t0 + dt / 3, tmp, fo, false);
+  tcomb(H, acc, acc, 3.0, fo);
+  tcomb(H, tmp, y, dt, fo, -dt / 3, cc);
+  tcomb(H, cc, cc, -1.0, fo);
+  tfield(n, w, ws, t0 + 2 * dt / 3, tmp, fo, false);
+  tcomb(H, acc, acc, 3.0, fo);
+  tcomb(H, tmp, y, dt, cc, dt, fo);
+  tfield(n, w, ws, t0 + dt, tmp, fo, false);
+  tcomb(H, acc, acc, 1.0, fo);
+  tcomb(H, y, y, dt / 8, acc);
+}
+
+// y <- the step from (t0, y) over dt; acc, cc, tmp, fo: scratch H-vectors
+__device__ __forceinline__ void tstep_fwd(const Net& n, const TileWork& w, double* ws, int method, double t0, double dt, double* y,
+                                          double* acc, double* cc, double* tmp, double* fo) {
+  const int H = n.H;
+  if (method == 0) {
+    tfield(n, w, ws, t0, y, fo, false);
+    tcomb(H, y, y, dt, fo);
+  } else if (method == 1) {
+    tfield(n, w, ws, t0, y, fo, false);
+    tcomb(H, tmp, y, dt / 2, fo);
+    tfield(n, w, ws, t0 + dt / 2, tmp, fo, false);
+    tcomb(H, y, y, dt, fo);
+  } else {
+    tfield(n, w, ws, t0, y, fo, false);
+    tstep_rk4(n, w, ws, t0, dt, y, fo, acc, cc, tmp, fo);
+  }
+}
+
+// the H-vectors of a fixed-grid sweep (tile_work: nh = 12), by name
+struct SweepVecs {
+  double *lam, *Y1, *Y2, *Y3, *Y4, *cc, *fo, *g4, *g3, *g2, *a, *gy;
+};
+__device__ __forceinline__ SweepVecs sweep_vecs(double* hv, int H) {
+  const long s = 16L * H;
+  return {hv, hv + s, hv + 2 * s, hv + 3 * s, hv + 4 * s, hv + 5 * s, hv + 6 * s, hv + 7 * s, hv + 8 * s, hv + 9 * s, hv + 10 * s,
+          hv + 11 * s};
+}
+
+// the reverse of the rk4 step y_l = step(y_{l-1}), y_{l-1} in v.Y1: v.lam, the cotangent of y_l, becomes that of y_{l-1}; the stages
+// are recomputed, parameter gradients go to slab (or none).  k1b (may be null): a further cotangent on k1 = F(t0, y_{l-1}).
+// For kt_adams_bwd's start-up steps; kt_ode_bwd keeps its own text of this sequence (see there).
+__device__ __forceinline__ void tstep_rk4_bwd(const Net& n, const TileWork& w, double* ws, double t0, double dt, const SweepVecs& v,
+                                              double* slab, const double* k1b) {
+  const int H = n.H;
+  double *lam = v.lam, *Y1 = v.Y1, *Y2 = v.Y2, *Y3 = v.Y3, *Y4 = v.Y4, *cc = v.cc, *fo = v.fo, *g4 = v.g4, *g3 = v.g3, *g2 = v.g2,
+         *a = v.a, *gy = v.gy;
+  tfield(n, w, ws, t0, Y1, fo, true);                        // k1; cc = k1
+  tcomb(H, cc, nullptr, 1.0, fo);
+  tcomb(H, Y2, Y1, dt / 3, fo);
+  tfield(n, w, ws, t0 + dt / 3, Y2, fo, true);               // k2
+  tcomb(H, Y3, Y1, dt, fo, -dt / 3, cc);
+  tcomb(H, cc, cc, -1.0, fo);                                // cc = k1 - k2
+  tfield(n, w, ws, t0 + 2 * dt / 3, Y3, fo, true);           // k3
+  tcomb(H, Y4, Y1, dt, cc, dt, fo);
+  tcomb(H, a, nullptr, dt / 8, lam);
+  tfield_vjp(n, w, ws, t0 + dt, Y4, a, g4, slab);
+  tcomb(H, a, nullptr, 3 * dt / 8, lam, dt, g4);
+  tfield_vjp(n, w, ws, t0 + 2 * dt / 3, Y3, a, g3, slab);
+  tcomb(H, a, nullptr, 3 * dt / 8, lam, -dt, g4, dt, g3);
+  tfield_vjp(n, w, ws, t0 + dt / 3, Y2, a, g2, slab);
+  for (int e = lane_id(); e < 16 * H; e += 64) {
+    double s = (dt / 8) * lam[e] + dt * g4[e] - (dt / 3) * g3[e] + (dt / 3) * g2[e];
+    if (k1b) s = s + k1b[e];
+    a[e] = s;
+  }
+  sync_tile();
+  tfield_vjp(n, w, ws, t0, Y1, a, gy, slab);
+  for (int e = lane_id(); e < 16 * H; e += 64) lam[e] += g4[e] + g3[e] + g2[e] + gy[e];
+  sync_tile();
+}
+
+// ---- the sweeps' shared ends ----------------------------------------------------------------------------------------------------
+// prologue: the start values, Sx = 0 and lam = 0, the tile's x and xproj
+__device__ __forceinline__ void sweep_prologue(const Net& n, const TileWork& w, double* ws, const XwOdeBwdJob& job, int p0, double* lam) {
+  const int N = job.N, l16 = lane_id() & 15;
+  double* st = ws + w.st;
+  double* Sx = ws + w.total - 16L * n.K;
+  if (lane_id() < 16) st[l16] = job.start[p0 + l16 < N ? p0 + l16 : N - 1];
+  for (int e = lane_id(); e < 16 * n.K; e += 64) Sx[e] = 0.0;
+  for (int e = lane_id(); e < 16 * n.H; e += 64) lam[e] = 0.0;
+  tile_x(n, w, ws, job.xT, N, p0);
+}
+
+// ub = the job's cotangent on u at time index l for the tile's paths, zero past the end of the job (the caller orders it)
+__device__ __forceinline__ void tcot_ub(const XwOdeBwdJob& job, int l, int L, int p0, double* ub) {
+  const int l16 = lane_id() & 15;
+  if (lane_id() < 16) ub[l16] = p0 + l16 < job.N ? cot_u(job, l, L, p0 + l16) : 0.0;
+}
+
+// slab's read-out entries for the output state v under the cotangent ub (both complete: behind a sync_tile)
+__device__ __forceinline__ void readout_grad(double* slab, const Net& n, const double* v, const double* ub) {
+  trowsum(slab, n.o.FLw, 1, n.H, v, ub, 1.0);
+  if (lane_id() == 0) {
+    double s = 0.0;
+    for (int p = 0; p < 16; ++p) s += ub[p];
+    slab[n.o.FLb] += s;
+  }
+}
+
+// the cotangent on u of time index l >= 1, whose output state is v (stored by the caller, needed with a slab only):
+// lam += FL_w ub, the read-out's gradient into slab
+__device__ __forceinline__ void tcot_output(const XwOdeBwdJob& job, const Net& n, int l, int L, int p0, double* ub, const double* v,
+                                            double* lam, double* slab) {
+  const double* flw = n.th + n.o.FLw;
+  tcot_ub(job, l, L, p0, ub);
+  sync_tile();
+  for (int e = lane_id(); e < 16 * n.H; e += 64) lam[e] = fma(flw[e >> 4], ub[e & 15], lam[e]);
+  if (slab) readout_grad(slab, n, v, ub);
+  sync_tile();
+}
+
+// tail, l = 0: read-out, then the lift 1 -> H -> H -> H, the x columns and the bias of the input layer; lam: the cotangent of y_0
+// from the steps.  With mode bit 2 the x-side outputs are those of the ALL-ONES cotangent while the parameter gradients use the
+// job's own (xw_generic.hip kg_ode_bwd).  p0v .. dh1: six scratch H-vectors.
+__device__ __forceinline__ void sweep_tail(const Net& n, const TileWork& w, double* ws, const XwOdeBwdJob& job, int L, int p0, int mode,
+                                           double* slab, const double* lam, double* p0v, double* p2v, double* y0, double* l0,
+                                           double* dh2, double* dh1) {
+  const int N = job.N, d = n.d, H = n.H, K = n.K, l16 = lane_id() & 15;
+  const bool want_x = (mode & 1) != 0, ones_x = (mode & 4) != 0;
+  const double* theta = n.th;
+  const double* flw = theta + n.o.FLw;
+  double* ub = ws + w.ub;
+  const double* st = ws + w.st;
+  const double* Sx = ws + w.total - 16L * K;
+  tcot_ub(job, 0, L, p0, ub);
+  sync_tile();
+  tlift(n, st, p0v, p2v, y0);
+  if (slab) readout_grad(slab, n, y0, ub);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 0 && !slab) continue;
+    if (pass == 1 && !(want_x && job.gs != nullptr)) continue;
+    const bool ones = pass == 1 && ones_x;
+    for (int e = lane_id(); e < 16 * H; e += 64) l0[e] = fma(flw[e >> 4], ones ? 1.0 : ub[e & 15], lam[e]);
+    sync_tile();
+    tgemm(theta + n.o.IL4w, 1, H, H, H, l0, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p2v, dh2);
+    tgemm(theta + n.o.IL2w, 1, H, H, H, dh2, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, p0v, dh1);
+    if (pass == 0) {
+      touter(slab, n.o.IL4w, H, H, H, l0, p2v, A_RELU);
+      touter(slab, n.o.IL2w, H, H, H, dh2, p0v, A_RELU);
+      trowsum(slab, n.o.IL4b, 1, H, l0, nullptr, 1.0);
+      trowsum(slab, n.o.IL2b, 1, H, dh2, nullptr, 1.0);
+      trowsum(slab, n.o.IL0w, 1, H, dh1, st, 1.0);
+      trowsum(slab, n.o.IL0b, 1, H, dh1, nullptr, 1.0);
+      sync_tile();
+    } else if (lane_id() < 16 && p0 + l16 < N) {
+      double s = 0.0;
+      for (int i = 0; i < H; ++i) s = fma(theta[n.o.IL0w + i], dh1[i * 16 + l16], s);
+      job.gs[p0 + l16] = s;
+    }
+  }
+  // the x columns and the bias of the input layer, from the summed cotangent of its pre-activation
+  if (slab) {
+    trowsum(slab, n.o.Winb, 1, K, Sx, nullptr, 1.0);
+    touter(slab, n.o.Win, n.o.ldin, K, d, Sx, ws + w.xt, A_PLAIN);
+  }
+  if (want_x && job.gx != nullptr) {
+    double* gxt = ws + w.xt + 16L * d;
+    tgemm(theta + n.o.Win, 1, n.o.ldin, d, K, Sx, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gxt);
+    tstore(d, N, p0, gxt, job.gx);
+  }
+}
+
+// host side: is this sweep job well-formed for `mode` (bit 0: x-side outputs, bit 1: parameter gradients, bit 2: all-ones x cotangent)?
+// (the state the sweep reverses -- Y, or the dopri5 record -- is the caller's to check)
+inline bool sweep_job_ok(const XwOdeBwdJob& j, int mode) {
+  if (!j.xT || !j.start || j.N < 1 || !cot_job_ok(j)) return false;
+  if ((mode & 2) && !j.gslab) return false;
+  return !((mode & 1) && !(mode & 4) && (!j.gx || !j.gs));
 }
 
 __device__ __forceinline__ void set_prio(int drop) {

@@ -3,9 +3,8 @@
 // kt_ode_fwd (xw_tiled.hip) takes one grid t[L] for all paths of a job.  Here path p of a job has its own non-decreasing times
 // tT[0 .. L)[p] (time-major, [L][N]); a path with fewer steps than L - 1 repeats its last time, and a zero-length step is the
 // exact identity of all three schemes (fma(0, k, y) == y), so its padded rows hold its final value.  One wave per 16-path tile,
-// kt_ode_fwd's workspace and stage sequences; t0 and dt live in a register per lane -- the lane's own path, column lane & 15 --
-// and reach the field's time term and the combinations through the per-path siblings of xw_tiled_blocks.h.  A job whose paths all
-// carry one grid reproduces kt_ode_fwd to the bit.
+// kt_ode_fwd's workspace and its step function (tstep_fwd of xw_tiled_blocks.h, which says why it takes them): t0 and dt live in a
+// register per lane -- the lane's own path, column lane & 15.  A job whose paths all carry one grid reproduces kt_ode_fwd to the bit.
 //
 // nstep[N] (optional): the index of each path's last distinct time.  A tile takes max(nstep) over its real paths as its step count
 // and fills the later rows with the state it has, without evaluating the field: the cost of a launch is the sum over tiles of
@@ -15,6 +14,7 @@
 #include "xnwan.h"
 
 namespace {
+#include "xw_generic_cot.h"   // (not used by this forward pass: the sweep helpers of xw_tiled_blocks.h name cot_u / cot_job_ok)
 #include "xw_tiled_blocks.h"
 
 __global__ void __launch_bounds__(64) kt_ode_fwd_pp(XwPathsJob job, const double* __restrict__ theta, int method, int L, int d, int H,
@@ -41,45 +41,14 @@ __global__ void __launch_bounds__(64) kt_ode_fwd_pp(XwPathsJob job, const double
     ns = mx < ns ? mx : ns;
   }
   const int rows = job.last_only ? ns + 1 : L;
-  const double* flw = theta + n.o.FLw;
   for (int l = 0; l < rows; ++l) {
     if (l > 0 && l <= ns) {
       const double t0 = job.tT[(long)(l - 1) * N + pc], dt = job.tT[(long)l * N + pc] - t0;
-      if (method == 0) {
-        tfield_pp(n, w, ws, t0, y, fo);
-        tcomb_pp(H, y, y, dt, fo);
-      } else if (method == 1) {
-        tfield_pp(n, w, ws, t0, y, fo);
-        tcomb_pp(H, tmp, y, dt / 2, fo);
-        tfield_pp(n, w, ws, t0 + dt / 2, tmp, fo);
-        tcomb_pp(H, y, y, dt, fo);
-      } else {                                                   // 3/8 rule: acc = k1 + 3 k2 + 3 k3 + k4, cc = k1 - k2
-        tfield_pp(n, w, ws, t0, y, fo);
-        tcomb_pp(H, acc, nullptr, 1.0, fo);
-        tcomb_pp(H, cc, nullptr, 1.0, fo);
-        tcomb_pp(H, tmp, y, dt / 3, fo);
-        tfield_pp(n, w, ws, t0 + dt / 3, tmp, fo);
-        tcomb_pp(H, acc, acc, 3.0, fo);
-        tcomb_pp(H, tmp, y, dt, fo, -dt / 3, cc);
-        tcomb_pp(H, cc, cc, -1.0, fo);
-        tfield_pp(n, w, ws, t0 + 2 * dt / 3, tmp, fo);
-        tcomb_pp(H, acc, acc, 3.0, fo);
-        tcomb_pp(H, tmp, y, dt, cc, dt, fo);
-        tfield_pp(n, w, ws, t0 + dt, tmp, fo);
-        tcomb_pp(H, acc, acc, 1.0, fo);
-        tcomb_pp(H, y, y, dt / 8, acc);
-      }
+      tstep_fwd(n, w, ws, method, t0, dt, y, acc, cc, tmp, fo);
     }
     if (job.last_only && l < ns) continue;
     const long row = job.last_only ? 0 : l;                      // (rows past ns: the state the tile has, stored again)
-    if (lane_id() < 16 && p0 + l16 < N) {
-      double u = theta[n.o.FLb];
-      for (int j = 0; j < H; ++j) u = fma(flw[j], y[j * 16 + l16], u);
-      job.u[row * N + p0 + l16] = u;
-    }
-    if (job.Y)
-      for (int e = lane_id(); e < 16 * H; e += 64)
-        if (p0 + (e & 15) < N) job.Y[(row * H + (e >> 4)) * N + p0 + (e & 15)] = y[e];
+    tput_output(n, job.u, job.Y, row, N, p0, y);
   }
 }
 
