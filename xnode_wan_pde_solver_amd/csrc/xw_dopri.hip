@@ -66,12 +66,7 @@ __global__ void __launch_bounds__(64) kd_init1(const Jobs<XwDopriJob> J, const d
   } else {
     acc[0] = acc[1] = 0.0;
   }
-  if (job_sum<2>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) {
-    const double cnt = (double)N * Hn;
-    const double d0 = sqrt(acc[0] / cnt), d1 = sqrt(acc[1] / cnt);
-    j.ctl[C_H0] = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    j.ctl[C_D1] = d1;
-  }
+  if (job_sum<2>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) ctl_init1(acc, N, Hn, j.ctl);
 }
 
 template <int HM>
@@ -98,26 +93,7 @@ __global__ void __launch_bounds__(64) kd_init2(const Jobs<XwDopriJob> J, const d
     acc[0] += r * r;
   }
   if (!active) acc[0] = 0.0;
-  if (job_sum<1>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) {
-    double* c = j.ctl;
-    const double d1 = c[C_D1], d2 = sqrt(acc[0] / ((double)N * Hn)) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
-    const double dt = fmin(100 * h0, h1);
-    const bool done = !(tf[L - 1] > t0);
-    c[C_T0] = t0;
-    c[C_DT] = dt;
-    c[C_NACC] = 0.0;
-    c[C_NATT] = 0.0;
-    c[C_DONE] = done ? 1.0 : 0.0;
-    c[C_STATUS] = 0.0;
-    c[C_RATIO] = 0.0;
-    c[C_GAP] = HUGE_VAL;
-    j.rec_t[0] = t0;
-    if (!done && !(t0 + dt > t0)) {                         // torchdiffeq: assert t0 + dt > t0, 'underflow in dt'
-      c[C_STATUS] = XW_DOPRI_UNDERFLOW;
-      c[C_DONE] = 1.0;
-    }
-  }
+  if (job_sum<1>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) ctl_init2(acc[0], N, Hn, tf, L, j.ctl, j.rec_t);
 }
 
 // One attempted step of every job that is not done.  The candidate y1 goes to record slot n_acc + 1 and f1 to the f buffer of the
@@ -191,48 +167,8 @@ __global__ void __launch_bounds__(64) kd_attempt(const Jobs<XwDopriJob> J, const
   } else {
     acc[0] = 0.0;
   }
-  if (!job_sum<1>(acc, j.work, c, nb, lb) || threadIdx.x != 0) return;
-  // the controller (torchdiffeq _adaptive_step / _optimal_step_size, order 5)
-  const double ratio = sqrt(acc[0] / ((double)N * Hn));
-  c[C_NATT] += 1.0;
-  c[C_RATIO] = ratio;
-  c[C_GAP] = fmin(c[C_GAP], fabs(ratio - 1.0));
-  if (ratio != ratio) {                                     // NaN: torchdiffeq rejects and its next dt is NaN (the underflow assert)
-    c[C_STATUS] = XW_DOPRI_NONFINITE;
-    c[C_DONE] = 1.0;
-    return;
-  }
-  const bool accept = ratio <= 1.0;
-  double dtn;
-  if (ratio == 0.0) {
-    dtn = dt * DP_IFACTOR;
-  } else {
-    const double dfac = ratio < 1.0 ? 1.0 : DP_DFACTOR;
-    dtn = dt * fmin(DP_IFACTOR, fmax(DP_SAFETY / pow(ratio, 1.0 / 5), dfac));
-  }
-  double tn = t0;
-  if (accept) {
-    if (!room) {
-      c[C_STATUS] = XW_DOPRI_CAPACITY;
-      c[C_DONE] = 1.0;
-      return;
-    }
-    j.rec_t[na + 1] = t1;
-    j.rec_h[na] = dt;
-    c[C_NACC] = (double)(na + 1);
-    tn = t1;
-  }
-  c[C_T0] = tn;
-  c[C_DT] = dtn;
-  if (!(tf[L - 1] > tn)) {
-    c[C_DONE] = 1.0;
-  } else if (accept && na + 1 >= max_steps) {
-    c[C_STATUS] = XW_DOPRI_STEPS;
-    c[C_DONE] = 1.0;
-  } else if (!(tn + dtn > tn)) {
-    c[C_STATUS] = XW_DOPRI_UNDERFLOW;
-    c[C_DONE] = 1.0;
-  }
+  if (job_sum<1>(acc, j.work, c, nb, lb) && threadIdx.x == 0)
+    ctl_attempt(acc[0], N, Hn, t0, dt, na, room, max_steps, tf, L, c, j.rec_t, j.rec_h);
 }
 
 // Reverse of the accepted steps (step sizes and grid constants), per path.  Step s: y_{s+1} = y_s + dt sum_j b_j k_j, stage j at
@@ -286,8 +222,7 @@ __global__ void __launch_bounds__(64) kd_sweep(const Jobs<XwDopriSweepJob> J, co
           for (int q = 0; q < 7; ++q) s_ = fma(k[q][h], w[q] * dt, s_);
           a[h] = y[h] + s_;                                    // the output state p(x_l)
         }
-        gadd_run(slab, n.o.FLw, H, active, [&](int h) { return ub * a[h]; });
-        gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub; });
+        path_readout_grad(slab, n, active, ub, a);
       }
       for (int h = 0; h < H; ++h) {
         const double yb = flw[h] * ub;
@@ -318,20 +253,17 @@ __global__ void __launch_bounds__(64) kd_sweep(const Jobs<XwDopriSweepJob> J, co
     const double ub = cot_u(job, l, L, path);
     if (slab) {
       for (int h = 0; h < H; ++h) a[h] = sj.rec_y[(long)h * N + path];
-      gadd_run(slab, n.o.FLw, H, active, [&](int h) { return ub * a[h]; });
-      gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub; });
+      path_readout_grad(slab, n, active, ub, a);
     }
     for (int h = 0; h < H; ++h) lam[h] = fma(flw[h], ub, lam[h]);
   }
   // l = 0: read-out, then the lift 1 -> H -> H -> H (src/model.py:78) -- the tail of kg_ode_bwd (xw_generic.hip); with mode bit 2
-  // the x-side outputs are those of the ALL-ONES cotangent while the parameter gradients use the job's own
+  // the x-side outputs are those of the ALL-ONES cotangent while the parameter gradients use the job's own.  A COPY of that tail,
+  // kept in step by hand: as one function for both kernels it cost kg_ode_bwd scratch and this kernel time (profiles/r19)
   const double ub0 = cot_u(job, 0, L, path);
   double p0[HM], p2[HM];
   lift(n, job.start[path], p0, p2, y);
-  if (slab) {
-    gadd_run(slab, n.o.FLw, H, active, [&](int h) { return ub0 * y[h]; });
-    gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub0; });
-  }
+  if (slab) path_readout_grad(slab, n, active, ub0, y);
   const double s0 = job.start[path];
   for (int pass = 0; pass < 2; ++pass) {
     if (pass == 0 && !slab) continue;
@@ -376,18 +308,6 @@ __global__ void __launch_bounds__(64) kd_sweep(const Jobs<XwDopriSweepJob> J, co
 }
 
 bool dims_ok(int L, int d, int H, int K, int m, int Hn) { return L >= 1 && xwg_ode_ok(d, H, K, m) && Hn >= 1 && Hn <= H; }
-
-int fwd_jobs(const XwDopriJob* jobs, int njobs, Jobs<XwDopriJob>& P) {
-  int e = pack_jobs(jobs, njobs, P);
-  if (e) return e;
-  for (int i = 0; i < njobs; ++i) {
-    const XwDopriJob& j = jobs[i];
-    if (!j.xT || !j.start || !j.u || !j.rec_y || !j.rec_t || !j.rec_h || !j.fbuf || !j.ctl || !j.work || j.N < 1 || j.cap < 0)
-      return XW_E_ARG;
-    P.blk0[i + 1] = P.blk0[i] + (j.N + 63) / 64;
-  }
-  return 0;
-}
 }  // namespace
 
 extern "C" int xw_dopri5_ctl_size(void) { return XW_DOPRI_CTL; }
@@ -398,7 +318,7 @@ extern "C" int xw_dopri5_init(const XwDopriJob* jobs, int njobs, const double* t
   if (!t || !theta || !(rtol >= 0.0) || !(atol >= 0.0)) return XW_E_ARG;
   if (!dims_ok(L, d, H, K, m, Hn)) return XW_E_DIMS;
   Jobs<XwDopriJob> P;
-  const int e = fwd_jobs(jobs, njobs, P);
+  const int e = fwd_jobs(jobs, njobs, P, 64);
   if (e) return e;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(P.blk0[njobs]), b(64);
@@ -417,7 +337,7 @@ extern "C" int xw_dopri5_attempts(const XwDopriJob* jobs, int njobs, const doubl
   if (!t || !theta || !(rtol >= 0.0) || !(atol >= 0.0) || max_steps < 1 || n < 0) return XW_E_ARG;
   if (!dims_ok(L, d, H, K, m, Hn)) return XW_E_DIMS;
   Jobs<XwDopriJob> P;
-  const int e = fwd_jobs(jobs, njobs, P);
+  const int e = fwd_jobs(jobs, njobs, P, 64);
   if (e) return e;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(P.blk0[njobs]), b(64);
@@ -435,22 +355,9 @@ extern "C" int xw_dopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const dou
   if (!t || !theta || L < 1 || (mode & ~7) || ((mode & 4) && (mode & 3) != 3)) return XW_E_ARG;
   if (!xwg_ode_ok(d, H, K, m)) return XW_E_DIMS;
   Jobs<XwDopriSweepJob> P;
-  int e = pack_jobs(jobs, njobs, P);
-  if (e) return e;
   hipStream_t s = (hipStream_t)stream;
-  const long Pu = u_offsets(d, H, K).total;
-  for (int i = 0; i < njobs; ++i) {
-    const XwDopriSweepJob& j = jobs[i];
-    if (!j.b.xT || !j.b.start || !j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || j.b.N < 1) return XW_E_ARG;
-    if (!cot_job_ok(j.b)) return XW_E_ARG;
-    if ((mode & 2) && !j.b.gslab) return XW_E_ARG;
-    if ((mode & 1) && !(mode & 4) && (!j.b.gx || !j.b.gs)) return XW_E_ARG;
-    if (mode & 2) {
-      const hipError_t he = hipMemsetAsync(j.b.gslab, 0, sizeof(double) * Pu * ((j.b.N + 15) / 16), s);
-      if (he != hipSuccess) return (int)he;
-    }
-    P.blk0[i + 1] = P.blk0[i] + (j.b.N + 63) / 64;
-  }
+  const int e = sweep_jobs(jobs, njobs, P, mode, u_offsets(d, H, K).total, 64, true, s);
+  if (e) return e;
   const dim3 g(P.blk0[njobs]), b(64);
   if (H <= 32)
     hipLaunchKernelGGL(kd_sweep<32>, g, b, 0, s, P, t, theta, L, d, H, K, m, mode);

@@ -1,7 +1,9 @@
 // xw_dopri_ctl.h -- what the two implementations of solver 'dopri5' share (xw_dopri.hip: the field per path on the vector ALU;
 // xw_tdopri.hip: the field per 16-path tile on the matrix pipe): the controller slots, the Dormand-Prince tableau, the dense
-// output, the job pack of a launch and the per-job ticket reduction.  Library-internal; included INSIDE an anonymous namespace,
-// after a gsum64(double) (the sum over the wave) has been declared.
+// output, the job pack of a launch, the per-job ticket reduction, the step controller (ctl_init1 / ctl_init2 / ctl_attempt: what the
+// lane that job_sum returns true on does with the totals) and the host side's job checks.  What stays with each implementation is
+// how a block or a tile forms its partial sums and where its vectors live.  Library-internal; included INSIDE an anonymous
+// namespace, after xw_generic_cot.h and after a gsum64(double) (the sum over the wave) has been declared.
 #pragma once
 
 // controller slots (include/xnwan.h)
@@ -42,7 +44,8 @@ __device__ __forceinline__ void dense_weights(double x, double (&w)[7]) {
 #define XW_DOPRI_MAXJOBS 8
 template <class J> struct Jobs {
   J j[XW_DOPRI_MAXJOBS];
-  int blk0[XW_DOPRI_MAXJOBS + 1];    // first block of every job, prefix sums of (N + 63) / 64
+  int blk0[XW_DOPRI_MAXJOBS + 1];    // first block of every job: prefix sums of the jobs' block counts (fwd_jobs / sweep_jobs;
+                                     // a block is 64 paths in xw_dopri.hip, one 16-path tile in xw_tdopri.hip)
   int njobs;
 };
 template <class J> __device__ __forceinline__ int job_of(const Jobs<J>& J_, int& lb) {
@@ -88,10 +91,124 @@ __device__ __forceinline__ bool job_sum(double (&val)[NV], double* __restrict__ 
   return true;
 }
 
+// ---- the step controller: lane 0 of the last block of a job, with the job's totals ---------------------------------------------
+// torchdiffeq _select_initial_step, first half: d0 = ||y0 / scale||, d1 = ||f0 / scale|| (acc: their squared sums), h0
+__device__ __forceinline__ void ctl_init1(const double (&acc)[2], int N, int Hn, double* c) {
+  const double cnt = (double)N * Hn;
+  const double d0 = sqrt(acc[0] / cnt), d1 = sqrt(acc[1] / cnt);
+  c[C_H0] = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  c[C_D1] = d1;
+}
+
+// second half: d2 from acc = the squared sum of (f(t0 + h0, y0 + h0 f0) - f0) / scale, the first step; the controller starts
+__device__ __forceinline__ void ctl_init2(double acc, int N, int Hn, const double* __restrict__ tf, int L, double* c, double* rec_t) {
+  const double t0 = tf[0], h0 = c[C_H0];
+  const double d1 = c[C_D1], d2 = sqrt(acc / ((double)N * Hn)) / h0;
+  const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
+  const double dt = fmin(100 * h0, h1);
+  const bool done = !(tf[L - 1] > t0);
+  c[C_T0] = t0;
+  c[C_DT] = dt;
+  c[C_NACC] = 0.0;
+  c[C_NATT] = 0.0;
+  c[C_DONE] = done ? 1.0 : 0.0;
+  c[C_STATUS] = 0.0;
+  c[C_RATIO] = 0.0;
+  c[C_GAP] = HUGE_VAL;
+  rec_t[0] = t0;
+  if (!done && !(t0 + dt > t0)) {                           // torchdiffeq: assert t0 + dt > t0, 'underflow in dt'
+    c[C_STATUS] = XW_DOPRI_UNDERFLOW;
+    c[C_DONE] = 1.0;
+  }
+}
+
+// after an attempt from t0 over dt with na steps accepted so far (torchdiffeq _adaptive_step / _optimal_step_size, order 5):
+// acc = the squared sum of the scaled error; room: the record has a slot for the candidate
+__device__ __forceinline__ void ctl_attempt(double acc, int N, int Hn, double t0, double dt, int na, bool room, int max_steps,
+                                            const double* __restrict__ tf, int L, double* c, double* rec_t, double* rec_h) {
+  const double t1 = t0 + dt;
+  const double ratio = sqrt(acc / ((double)N * Hn));
+  c[C_NATT] += 1.0;
+  c[C_RATIO] = ratio;
+  c[C_GAP] = fmin(c[C_GAP], fabs(ratio - 1.0));
+  if (ratio != ratio) {                                     // NaN: torchdiffeq rejects and its next dt is NaN (the underflow assert)
+    c[C_STATUS] = XW_DOPRI_NONFINITE;
+    c[C_DONE] = 1.0;
+    return;
+  }
+  const bool accept = ratio <= 1.0;
+  double dtn;
+  if (ratio == 0.0) {
+    dtn = dt * DP_IFACTOR;
+  } else {
+    const double dfac = ratio < 1.0 ? 1.0 : DP_DFACTOR;
+    dtn = dt * fmin(DP_IFACTOR, fmax(DP_SAFETY / pow(ratio, 1.0 / 5), dfac));
+  }
+  double tn = t0;
+  if (accept) {
+    if (!room) {
+      c[C_STATUS] = XW_DOPRI_CAPACITY;
+      c[C_DONE] = 1.0;
+      return;
+    }
+    rec_t[na + 1] = t1;
+    rec_h[na] = dt;
+    c[C_NACC] = (double)(na + 1);
+    tn = t1;
+  }
+  c[C_T0] = tn;
+  c[C_DT] = dtn;
+  if (!(tf[L - 1] > tn)) {
+    c[C_DONE] = 1.0;
+  } else if (accept && na + 1 >= max_steps) {
+    c[C_STATUS] = XW_DOPRI_STEPS;
+    c[C_DONE] = 1.0;
+  } else if (!(tn + dtn > tn)) {
+    c[C_STATUS] = XW_DOPRI_UNDERFLOW;
+    c[C_DONE] = 1.0;
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
 template <class J> int pack_jobs(const J* jobs, int njobs, Jobs<J>& P) {
   if (!jobs || njobs < 1 || njobs > XW_DOPRI_MAXJOBS) return XW_E_ARG;
   P.njobs = njobs;
   P.blk0[0] = 0;
   for (int i = 0; i < njobs; ++i) P.j[i] = jobs[i];
-  return 0;                                                 // (blk0: by the caller, from the job kind's N)
+  return 0;                                                 // (blk0: below, from the job kind's N)
+}
+
+// the jobs of a forward launch (init, attempts), paths_per_block paths to a block
+inline int fwd_jobs(const XwDopriJob* jobs, int njobs, Jobs<XwDopriJob>& P, int paths_per_block) {
+  const int e = pack_jobs(jobs, njobs, P);
+  if (e) return e;
+  for (int i = 0; i < njobs; ++i) {
+    const XwDopriJob& j = jobs[i];
+    if (!j.xT || !j.start || !j.u || !j.rec_y || !j.rec_t || !j.rec_h || !j.fbuf || !j.ctl || !j.work || j.N < 1 || j.cap < 0)
+      return XW_E_ARG;
+    P.blk0[i + 1] = P.blk0[i] + (j.N + paths_per_block - 1) / paths_per_block;
+  }
+  return 0;
+}
+
+// the jobs of a sweep launch: record and job well-formed for `mode`, the slabs (Pu doubles per 16 paths) zeroed with mode bit 1.
+// zero_each: a job's slabs as soon as the job has passed, so that a failed memset is reported ahead of a later job's XW_E_ARG
+// (xw_dopri5_sweep); else once every job has passed (xw_tdopri5_sweep)
+inline int sweep_jobs(const XwDopriSweepJob* jobs, int njobs, Jobs<XwDopriSweepJob>& P, int mode, long Pu, int paths_per_block,
+                      bool zero_each, hipStream_t s) {
+  const int e = pack_jobs(jobs, njobs, P);
+  if (e) return e;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < njobs; ++i) {
+      const XwDopriSweepJob& j = jobs[i];
+      if (pass == 0) {
+        if (!j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || !sweep_job_ok(j.b, mode)) return XW_E_ARG;
+        P.blk0[i + 1] = P.blk0[i] + (j.b.N + paths_per_block - 1) / paths_per_block;
+      }
+      if ((mode & 2) && zero_each == (pass == 0)) {
+        const hipError_t he = hipMemsetAsync(j.b.gslab, 0, sizeof(double) * Pu * ((j.b.N + 15) / 16), s);
+        if (he != hipSuccess) return (int)he;
+      }
+    }
+  return 0;
 }

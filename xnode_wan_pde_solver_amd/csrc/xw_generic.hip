@@ -89,10 +89,7 @@ __global__ void __launch_bounds__(64) kg_ode_bwd(XwOdeBwdJob job, const double* 
       y[j] = job.Y[((long)l * H + j) * N + path];
       lam[j] = fma(flw[j], ub, lam[j]);
     }
-    if (slab) {
-      gadd_run(slab, n.o.FLw, H, active, [&](int j) { return ub * y[j]; });
-      gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub; });
-    }
+    if (slab) path_readout_grad(slab, n, active, ub, y);
     // y_l = step(y_{l-1}): lam becomes the cotangent of y_{l-1}
     const double t0 = tf[l - 1], dt = tf[l] - tf[l - 1];
     for (int j = 0; j < H; ++j) y[j] = job.Y[((long)(l - 1) * H + j) * N + path];
@@ -134,14 +131,13 @@ __global__ void __launch_bounds__(64) kg_ode_bwd(XwOdeBwdJob job, const double* 
     }
   }
   // l = 0: read-out, then the lift 1 -> H -> H -> H (src/model.py:78); with mode bit 2 the x-side outputs are those of the
-  // ALL-ONES cotangent (the helper backward of src/loss.py:55) while the parameter gradients use the job's own
+  // ALL-ONES cotangent (the helper backward of src/loss.py:55) while the parameter gradients use the job's own.  kd_sweep
+  // (xw_dopri.hip) ends in a copy of this tail: shared as one function it changed which field_vjp calls the inliner expands
+  // here and the frame grew (profiles/r19), so a change to either copy goes into both
   const double ub0 = cot_u(job, 0, L, path);
   double p0[GH], p2[GH];
   lift(n, job.start[path], p0, p2, y);
-  if (slab) {
-    gadd_run(slab, n.o.FLw, H, active, [&](int j) { return ub0 * y[j]; });
-    gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub0; });
-  }
+  if (slab) path_readout_grad(slab, n, active, ub0, y);
   const double s = job.start[path];
   for (int pass = 0; pass < 2; ++pass) {
     // pass 0: parameter gradients (cotangent ub0); pass 1: d/d start (cotangent 1 with mode bit 2, else ub0)
@@ -436,10 +432,7 @@ int xwg_ode_bwd_multi(const XwOdeBwdJob* jobs, int njobs, const double* t, const
   const long P = u_offsets(d, H, K).total;
   for (int i = 0; i < njobs; ++i) {
     const XwOdeBwdJob& j = jobs[i];
-    if (!j.xT || !j.start || !j.Y || j.N < 1) return XW_E_ARG;
-    if (!cot_job_ok(j)) return XW_E_ARG;
-    if ((mode & 2) && !j.gslab) return XW_E_ARG;
-    if ((mode & 1) && !(mode & 4) && (!j.gx || !j.gs)) return XW_E_ARG;
+    if (!j.Y || !sweep_job_ok(j, mode)) return XW_E_ARG;
     if (mode & 2) {
       const hipError_t e = hipMemsetAsync(j.gslab, 0, sizeof(double) * P * ((j.N + 15) / 16), s);
       if (e != hipSuccess) return (int)e;

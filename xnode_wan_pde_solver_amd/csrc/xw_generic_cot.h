@@ -1,5 +1,5 @@
-// xw_generic_cot.h -- the cotangent on u of a sweep job (XwOdeBwdJob: stored, all ones or a residual form), per path.
-// Library-internal; included INSIDE an anonymous namespace, after xw_generic_field.h.
+// xw_generic_cot.h -- the cotangent on u of a sweep job (XwOdeBwdJob: stored, all ones or a residual form), per path, and the
+// host side's check of such a job.  Library-internal; included INSIDE an anonymous namespace, after xw_common.h and xnwan.h.
 #pragma once
 // the weak form's dI/du at (l, path) -- kind 2, and the B part of kind 3
 __device__ __forceinline__ double cot_weak(const XwOdeBwdJob& j, int l, int L, int path, long p) {
@@ -31,4 +31,11 @@ inline bool cot_job_ok(const XwOdeBwdJob& j) {
   if (j.res_first_only >= 2 && (j.res_w == nullptr || (!j.res_c != !j.res_cp))) return false;
   if (j.res_first_only == 3 && (j.res_scal == nullptr || j.res_refA == nullptr)) return false;
   return true;
+}
+// host side: is this sweep job well-formed for `mode` (bit 0: x-side outputs, bit 1: parameter gradients, bit 2: all-ones x cotangent)?
+// (the state the sweep reverses -- Y, or the dopri5 record -- is the caller's to check)
+inline bool sweep_job_ok(const XwOdeBwdJob& j, int mode) {
+  if (!j.xT || !j.start || j.N < 1 || !cot_job_ok(j)) return false;
+  if ((mode & 2) && !j.gslab) return false;
+  return !((mode & 1) && !(mode & 4) && (!j.gx || !j.gs));
 }

@@ -1,5 +1,6 @@
 // xw_generic_field.h -- u_theta per path on the vector ALU: the field, its vector-Jacobian product, the lift and the
-// x-projection, and the deterministic slab accumulation (xw_generic.hip; also the dopri5 kernels of xw_dopri.hip).
+// x-projection, the deterministic slab accumulation and the read-out's gradient (xw_generic.hip; also the dopri5 kernels of
+// xw_dopri.hip).
 // Library-internal; included INSIDE an anonymous namespace, after xw_common.h and xw_generic.h.
 #pragma once
 constexpr int GH = XWG_MAX_H, GK = XWG_MAX_K, GW = XWG_MAX_W, GM = XWG_MAX_M, GQ = XWG_MAX_Q;
@@ -107,6 +108,12 @@ __device__ __forceinline__ void gadd_run(double* slab, int e0, int n, bool activ
     }
     if (c + l16 < n) slab[e0 + c + l16] += mine;
   }
+}
+
+// slab's read-out entries (FL_w, FL_b) for the output state y under the cotangent ub
+__device__ __forceinline__ void path_readout_grad(double* slab, const Net& n, bool active, double ub, const double* y) {
+  gadd_run(slab, n.o.FLw, n.H, active, [&](int h) { return ub * y[h]; });
+  gadd_run(slab, n.o.FLb, 1, active, [&](int) { return ub; });
 }
 
 // a^T dF/d(y, theta) at (t, yin): gy[H] (overwritten), Sx[K] += cotangent of the input layer's pre-activation (the x columns and

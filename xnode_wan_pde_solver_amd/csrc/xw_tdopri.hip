@@ -91,12 +91,7 @@ __global__ void __launch_bounds__(64) kq_init1(const Jobs<XwDopriJob> J, const d
   tstore(H, N, p0, f, j.fbuf);
   for (int l = 0; l < L; ++l)                               // t_0 (and sample times that do not lie past it) give y0 itself
     if (l == 0 || !(tf[l] > tf[0])) tput_output(n, j.u, j.Y, l, N, p0, y);
-  if (job_sum<2>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) {
-    const double cnt = (double)N * Hn;
-    const double d0 = sqrt(acc[0] / cnt), d1 = sqrt(acc[1] / cnt);
-    j.ctl[C_H0] = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    j.ctl[C_D1] = d1;
-  }
+  if (job_sum<2>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) ctl_init1(acc, N, Hn, j.ctl);
 }
 
 __global__ void __launch_bounds__(64) kq_init2(const Jobs<XwDopriJob> J, const double* __restrict__ tf, const double* __restrict__ theta,
@@ -124,26 +119,7 @@ __global__ void __launch_bounds__(64) kq_init2(const Jobs<XwDopriJob> J, const d
     const double r = (f1[e] - f0[e]) / (atol + rtol * fabs(y0[e]));
     acc[0] += r * r;
   }
-  if (job_sum<1>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) {
-    double* c = j.ctl;
-    const double d1 = c[C_D1], d2 = sqrt(acc[0] / ((double)N * Hn)) / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
-    const double dt = fmin(100 * h0, h1);
-    const bool done = !(tf[L - 1] > t0);
-    c[C_T0] = t0;
-    c[C_DT] = dt;
-    c[C_NACC] = 0.0;
-    c[C_NATT] = 0.0;
-    c[C_DONE] = done ? 1.0 : 0.0;
-    c[C_STATUS] = 0.0;
-    c[C_RATIO] = 0.0;
-    c[C_GAP] = HUGE_VAL;
-    j.rec_t[0] = t0;
-    if (!done && !(t0 + dt > t0)) {                         // torchdiffeq: assert t0 + dt > t0, 'underflow in dt'
-      c[C_STATUS] = XW_DOPRI_UNDERFLOW;
-      c[C_DONE] = 1.0;
-    }
-  }
+  if (job_sum<1>(acc, j.work, j.ctl, nb, lb) && threadIdx.x == 0) ctl_init2(acc[0], N, Hn, tf, L, j.ctl, j.rec_t);
 }
 
 // One attempted step of every job that is not done (kd_attempt of xw_dopri.hip on tiles).  The candidate y1 goes to record slot
@@ -205,48 +181,8 @@ __global__ void __launch_bounds__(64) kq_attempt(const Jobs<XwDopriJob> J, const
     tput_output(n, j.u, j.Y, l, N, p0, pv);
     sync_tile();
   }
-  if (!job_sum<1>(acc, j.work, c, nb, lb) || threadIdx.x != 0) return;
-  // the controller (torchdiffeq _adaptive_step / _optimal_step_size, order 5)
-  const double ratio = sqrt(acc[0] / ((double)N * Hn));
-  c[C_NATT] += 1.0;
-  c[C_RATIO] = ratio;
-  c[C_GAP] = fmin(c[C_GAP], fabs(ratio - 1.0));
-  if (ratio != ratio) {                                     // NaN: torchdiffeq rejects and its next dt is NaN (the underflow assert)
-    c[C_STATUS] = XW_DOPRI_NONFINITE;
-    c[C_DONE] = 1.0;
-    return;
-  }
-  const bool accept = ratio <= 1.0;
-  double dtn;
-  if (ratio == 0.0) {
-    dtn = dt * DP_IFACTOR;
-  } else {
-    const double dfac = ratio < 1.0 ? 1.0 : DP_DFACTOR;
-    dtn = dt * fmin(DP_IFACTOR, fmax(DP_SAFETY / pow(ratio, 1.0 / 5), dfac));
-  }
-  double tn = t0;
-  if (accept) {
-    if (!room) {
-      c[C_STATUS] = XW_DOPRI_CAPACITY;
-      c[C_DONE] = 1.0;
-      return;
-    }
-    j.rec_t[na + 1] = t1;
-    j.rec_h[na] = dt;
-    c[C_NACC] = (double)(na + 1);
-    tn = t1;
-  }
-  c[C_T0] = tn;
-  c[C_DT] = dtn;
-  if (!(tf[L - 1] > tn)) {
-    c[C_DONE] = 1.0;
-  } else if (accept && na + 1 >= max_steps) {
-    c[C_STATUS] = XW_DOPRI_STEPS;
-    c[C_DONE] = 1.0;
-  } else if (!(tn + dtn > tn)) {
-    c[C_STATUS] = XW_DOPRI_UNDERFLOW;
-    c[C_DONE] = 1.0;
-  }
+  if (job_sum<1>(acc, j.work, c, nb, lb) && threadIdx.x == 0)
+    ctl_attempt(acc[0], N, Hn, t0, dt, na, room, max_steps, tf, L, c, j.rec_t, j.rec_h);
 }
 
 // Reverse of the accepted steps (step sizes and grid constants), per tile: kd_sweep of xw_dopri.hip on tiles.  Step s:
@@ -353,18 +289,6 @@ int fwd_check(int njobs, const double* t, const double* theta, int L, int d, int
   if (Hn < 1 || Hn > H) return XW_E_ARG;
   return 0;
 }
-
-int fwd_jobs(const XwDopriJob* jobs, int njobs, Jobs<XwDopriJob>& P) {
-  const int e = pack_jobs(jobs, njobs, P);
-  if (e) return e;
-  for (int i = 0; i < njobs; ++i) {
-    const XwDopriJob& j = jobs[i];
-    if (!j.xT || !j.start || !j.u || !j.rec_y || !j.rec_t || !j.rec_h || !j.fbuf || !j.ctl || !j.work || j.N < 1 || j.cap < 0)
-      return XW_E_ARG;
-    P.blk0[i + 1] = P.blk0[i] + (j.N + 15) / 16;              // (tiles)
-  }
-  return 0;
-}
 }  // namespace
 
 extern "C" int xw_tdopri5_work(int sweep, int d, int H, int K, int m) {
@@ -379,7 +303,7 @@ extern "C" int xw_tdopri5_init(const XwDopriJob* jobs, int njobs, const double* 
   int e = fwd_check(njobs, t, theta, L, d, H, K, m, Hn, rtol, atol, work);
   if (e) return e;
   Jobs<XwDopriJob> P;
-  e = fwd_jobs(jobs, njobs, P);
+  e = fwd_jobs(jobs, njobs, P, 16);
   if (e) return e;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(P.blk0[njobs]), b(64);
@@ -395,7 +319,7 @@ extern "C" int xw_tdopri5_attempts(const XwDopriJob* jobs, int njobs, const doub
   if (e) return e;
   if (max_steps < 1 || n < 0) return XW_E_ARG;
   Jobs<XwDopriJob> P;
-  e = fwd_jobs(jobs, njobs, P);
+  e = fwd_jobs(jobs, njobs, P, 16);
   if (e) return e;
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(P.blk0[njobs]), b(64);
@@ -410,20 +334,9 @@ extern "C" int xw_tdopri5_sweep(const XwDopriSweepJob* jobs, int njobs, const do
   if ((mode & 3) == 0 || (mode & ~31) || ((mode & 4) && (mode & 3) != 3)) return XW_E_ARG;
   if (!dims_ok(d, H, K, m) || (mode & (8 | 16))) return XW_E_DIMS;   // (no continuous adjoint, no narrow tiles in this family)
   Jobs<XwDopriSweepJob> P;
-  const int e = pack_jobs(jobs, njobs, P);
-  if (e) return e;
   hipStream_t s = (hipStream_t)stream;
-  const long Pu = u_offsets(d, H, K).total;
-  for (int i = 0; i < njobs; ++i) {
-    const XwDopriSweepJob& j = jobs[i];
-    if (!j.rec_y || !j.rec_t || !j.rec_h || !j.ctl || !sweep_job_ok(j.b, mode)) return XW_E_ARG;
-    P.blk0[i + 1] = P.blk0[i] + (j.b.N + 15) / 16;
-  }
-  if (mode & 2)
-    for (int i = 0; i < njobs; ++i) {
-      const hipError_t he = hipMemsetAsync(jobs[i].b.gslab, 0, sizeof(double) * Pu * ((jobs[i].b.N + 15) / 16), s);
-      if (he != hipSuccess) return (int)he;
-    }
+  const int e = sweep_jobs(jobs, njobs, P, mode, u_offsets(d, H, K).total, 16, false, s);
+  if (e) return e;
   hipLaunchKernelGGL(kq_sweep, dim3(P.blk0[njobs]), dim3(64), 0, s, P, t, theta, L, d, H, K, m, mode, work);
   return xw_launch_status();
 }

@@ -1,8 +1,8 @@
 // xw_tiled_blocks.h -- the building blocks of the tiled stepper family: the per-tile workspace; the tile products, field, VJP, lift
 // and combinations; and the sequences its kernels share -- the fixed-grid step, the rk4 reverse, the output block, the cotangent on
-// u of a time index, the sweeps' prologue and tail, the host's check of a sweep job.  Used by xw_tiled.hip, xw_tiled_paths.hip and
+// u of a time index, the sweeps' prologue and tail.  Used by xw_tiled.hip, xw_tiled_paths.hip and
 // xw_tdopri.hip; kt_ode_bwd alone keeps its own text of the sweep pieces (xw_tiled.hip says why).  Library-internal; included INSIDE an anonymous namespace, after xw_common.h, xnwan.h and
-// xw_generic_cot.h (cot_u, cot_job_ok).
+// xw_generic_cot.h (cot_u; the host's check of a sweep job, sweep_job_ok, is there too).
 #pragma once
 
 #define XWT_MAX_H 256
@@ -413,14 +413,6 @@ __device__ __forceinline__ void sweep_tail(const Net& n, const TileWork& w, doub
     tgemm(theta + n.o.Win, 1, n.o.ldin, d, K, Sx, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gxt);
     tstore(d, N, p0, gxt, job.gx);
   }
-}
-
-// host side: is this sweep job well-formed for `mode` (bit 0: x-side outputs, bit 1: parameter gradients, bit 2: all-ones x cotangent)?
-// (the state the sweep reverses -- Y, or the dopri5 record -- is the caller's to check)
-inline bool sweep_job_ok(const XwOdeBwdJob& j, int mode) {
-  if (!j.xT || !j.start || j.N < 1 || !cot_job_ok(j)) return false;
-  if ((mode & 2) && !j.gslab) return false;
-  return !((mode & 1) && !(mode & 4) && (!j.gx || !j.gs));
 }
 
 __device__ __forceinline__ void set_prio(int drop) {

@@ -509,6 +509,10 @@ DOPRI5_CHUNK, DOPRI5_MAX_STEPS = 8, 10000  # attempts per host check; accepted s
 DOPRI5_MAXJOBS = 8                         # jobs per launch (csrc/xw_dopri_ctl.h XW_DOPRI_MAXJOBS)
 DOPRI5_STEPPERS = ('vector', 'tiled')      # the two implementations: csrc/xw_dopri.hip (the field per path on the vector ALU, up to
                                            # GENERIC_ODE_MAX) and csrc/xw_tdopri.hip (per 16-path tile on the MFMA, up to TILED_ODE_MAX)
+# per stepper: the init, attempts and sweep entry points, the size of a record's partial sums (per 64-path block, or per 16-path
+# tile), and whether the launches take a workspace (_dopri5_tiled_work) ahead of the stream
+_DOPRI5_ENTRY = {'vector': ('xw_dopri5_init', 'xw_dopri5_attempts', 'xw_dopri5_sweep', 'xw_dopri5_work_size', False),
+                 'tiled': ('xw_tdopri5_init', 'xw_tdopri5_attempts', 'xw_tdopri5_sweep', 'xw_tdopri5_part_size', True)}
 CTL_T0, CTL_DT, CTL_NACC, CTL_NATT, CTL_DONE, CTL_STATUS, CTL_RATIO, CTL_GAP = 0, 1, 2, 3, 4, 5, 8, 9
 
 
@@ -558,8 +562,8 @@ class Dopri5Record:
         self.rec_t = torch.empty(cap + 1, dtype=F64, device=dev)
         self.rec_h = torch.empty(max(cap, 1), dtype=F64, device=dev)
         self.fbuf = torch.empty(2, H, N, dtype=F64, device=dev)
-        # (the partial sums of the forward's reductions: per 64-path block, or per 16-path tile -- the sweeps do not read them)
-        self.work = torch.empty((lib.xw_tdopri5_part_size if stepper == 'tiled' else lib.xw_dopri5_work_size)(N), dtype=F64, device=dev)
+        # (the partial sums of the forward's reductions -- the sweeps do not read them)
+        self.work = torch.empty(getattr(lib, _DOPRI5_ENTRY[stepper][3])(N), dtype=F64, device=dev)
         self.n_acc = self.n_att = 0
         self.grid = self.min_gap = self.steps = None
 
@@ -585,7 +589,7 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
     status raises XnwanError.  Synchronises with the host: a dopri5 forward cannot be captured into a graph.
     stepper: 'vector' (xw_dopri5_*) or 'tiled' (xw_tdopri5_*: H, K up to 256, m up to 32; one workspace for all its launches)."""
     _need_gpu()
-    tiled = dopri5_stepper(stepper) == 'tiled'
+    init, attempts, _, _, takes_work = _DOPRI5_ENTRY[dopri5_stepper(stepper)]
     if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
         raise XnwanError('dopri5_fwd: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
     chunk, max_steps = int(chunk), int(max_steps)
@@ -605,7 +609,8 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
         _chk(j.get('Y'), F64, (L, H, N), 'Y')
         recs.append(Dopri5Record(N, H, int(cap) if cap else 4 * chunk, dev, stepper))
     arr = (XwDopriJob * nj)()
-    work = _dopri5_tiled_work(False, d, H, K, m, [r.N for r in recs], dev) if tiled else None
+    work = _dopri5_tiled_work(False, d, H, K, m, [r.N for r in recs], dev) if takes_work else None
+    tail = (_p(work), _stream()) if takes_work else (_stream(),)
 
     def fill():
         for i, (a, j, r) in enumerate(zip(arr, jobs, recs)):
@@ -614,10 +619,7 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
             a.ctl, a.work, a.N, a.cap = _p(ctl[i]), _p(r.work), r.N, r.cap
     args = (_p(t), _p(theta), L, d, H, K, m, int(Hn), float(rtol), float(atol))
     fill()
-    if tiled:
-        check(lib.xw_tdopri5_init(arr, nj, *args, _p(work), _stream()), 'xw_tdopri5_init')
-    else:
-        check(lib.xw_dopri5_init(arr, nj, *args, _stream()), 'xw_dopri5_init')
+    check(getattr(lib, init)(arr, nj, *args, *tail), init)
     ev = torch.cuda.Event()
     n_acc = [0] * nj
     while True:
@@ -628,10 +630,7 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
                 grown = True
         if grown:
             fill()
-        if tiled:
-            check(lib.xw_tdopri5_attempts(arr, nj, *args, max_steps, chunk, _p(work), _stream()), 'xw_tdopri5_attempts')
-        else:
-            check(lib.xw_dopri5_attempts(arr, nj, *args, max_steps, chunk, _stream()), 'xw_dopri5_attempts')
+        check(getattr(lib, attempts)(arr, nj, *args, max_steps, chunk, *tail), attempts)
         mirror.copy_(ctl, non_blocking=True)
         ev.record()
         ev.synchronize()
@@ -668,7 +667,7 @@ def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False,
     layouts as ode_bwd_multi (mode bits 0..2).  stepper: 'vector' (xw_dopri5_sweep) or 'tiled' (xw_tdopri5_sweep); either reverses
     a record of either forward at widths both serve."""
     _need_gpu()
-    tiled = dopri5_stepper(stepper) == 'tiled'
+    _, _, sweep, _, takes_work = _DOPRI5_ENTRY[dopri5_stepper(stepper)]
     if not 1 <= len(jobs) <= DOPRI5_MAXJOBS:
         raise XnwanError('dopri5_sweep: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
     if x_cot_ones and not (want_x and want_params):
@@ -694,11 +693,9 @@ def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False,
         _set_res(b, j, L, N)
         a.rec_y, a.rec_t, a.rec_h, a.ctl = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.ctl)
     mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0)
-    if tiled:
-        work = _dopri5_tiled_work(True, d, H, K, m, [a.b.N for a in arr], t.device)
-        check(lib.xw_tdopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _p(work), _stream()), 'xw_tdopri5_sweep')
-    else:
-        check(lib.xw_dopri5_sweep(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _stream()), 'xw_dopri5_sweep')
+    work = _dopri5_tiled_work(True, d, H, K, m, [a.b.N for a in arr], t.device) if takes_work else None
+    tail = (_p(work), _stream()) if takes_work else (_stream(),)
+    check(getattr(lib, sweep)(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, *tail), sweep)
 
 
 DISC_UNROLLED_DEPTH = 9   # v_layers of the reference's YAML: the depth the recomputing reverse kernels are compiled for
