@@ -1374,6 +1374,7 @@ int launch_fwd(int method, const FwdJobs& jobs, const double* t, const double* t
   return xw_launch_status();
 }
 
+#include "xw_generic_cot.h"   // (the host's check of a sweep job, sweep_job_ok; the cotangent's device text there is not used here)
 }  // namespace
 
 #ifndef XW_ODE_PART_RECOMP
@@ -1418,12 +1419,8 @@ extern "C" int XW_ODE_FN(xw_ode_bwd_multi_w)(const XwOdeBwdJob* jobs, int njobs,
   J.tile0[0] = 0;
   for (int i = 0; i < XW_MAXJOBS; ++i) {
     const bool on = i < njobs;
-    if (on) {
-      if (!jobs[i].xT || !jobs[i].start || !jobs[i].Y || jobs[i].N <= 0) return XW_E_ARG;
-      if ((mode & 2) && !jobs[i].gslab) return XW_E_ARG;
-      if ((mode & 1) && !(mode & 4) && (!jobs[i].gx || !jobs[i].gs)) return XW_E_ARG;
-      if ((mode & 1) && (!jobs[i].gx != !jobs[i].gs)) return XW_E_ARG;
-    }
+    if (on && (!jobs[i].Y || !sweep_job_ok(jobs[i], mode))) return XW_E_ARG;      // (xw_generic_cot.h: as every family's entry point)
+    if (on && (mode & 1) && (!jobs[i].gx != !jobs[i].gs)) return XW_E_ARG;
     J.xT[i] = on ? jobs[i].xT : nullptr;
     J.start[i] = on ? jobs[i].start : nullptr;
     J.Y[i] = on ? jobs[i].Y : nullptr;
@@ -1444,10 +1441,6 @@ extern "C" int XW_ODE_FN(xw_ode_bwd_multi_w)(const XwOdeBwdJob* jobs, int njobs,
     J.res_refA[i] = on ? jobs[i].res_refA : nullptr;
     J.res_coefA[i] = on ? jobs[i].res_coefA : 0.0;
     J.res_baseA[i] = on ? jobs[i].res_baseA : 0.0;
-    if (on && jobs[i].res_u && (!jobs[i].res_ref || jobs[i].ubar)) return XW_E_ARG;
-    if (on && jobs[i].res_u && jobs[i].res_first_only >= 2 && (!jobs[i].res_w || (!jobs[i].res_c != !jobs[i].res_cp))) return XW_E_ARG;
-    if (on && (jobs[i].res_first_only < 0 || jobs[i].res_first_only > 3)) return XW_E_ARG;
-    if (on && jobs[i].res_first_only == 3 && (!jobs[i].res_u || !jobs[i].res_scal || !jobs[i].res_refA)) return XW_E_ARG;
     J.gx[i] = (on && (mode & 1)) ? jobs[i].gx : nullptr;
     J.gs[i] = (on && (mode & 1)) ? jobs[i].gs : nullptr;
     J.gslab[i] = (on && (mode & 2)) ? jobs[i].gslab : nullptr;

@@ -1221,6 +1221,20 @@ class Engine:
             j = dict(xT=G.xbT, start=G.start_b, u=G.ub, Y=G.Yb, act=G.act_b, ubar=ubar, gslab=gslab)
         return j
 
+    # The residual forms of the generator's sweeps (kernels._set_res), each once: what csrc/xw_substep.hip restates for the runner's groups
+    def _res_init(self, G):      # cotangent A: pollution + the initial-value penalty at t_0
+        # (pairwise group: the initial penalty is the mean over all PAIRS (u_n - h_m)^2, whose u-gradient is 2 (u_n - mean h) / N)
+        return dict(u=G.u, ref=G.href if G.pair_i else G.h, coef=2.0 * self.alpha / G.Nglob, base=self.pollution, first_only=True)
+
+    def _res_bdry(self, G):      # the boundary penalty's cotangent (only for a group with boundary paths: Nbglob Lb > 0)
+        return dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
+
+    def _res_weak(self, G):      # cotangent B = dI/du, a pointwise product of what the two forward passes wrote (kind 2)
+        return dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob, weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck))
+
+    def _res_merged(self, G):    # kind 3, A + (2 / I) B: B with A's ref, coef and base (_merged_ok: no pairwise group, ref = h) and I = scal[0]
+        return dict(self._res_weak(G), merged=dict(self._res_init(G), scal=self.scal))
+
     def _contract(self, G, adam_state=None, with_bdry=False):
         """I, sum v^2, SSE_init from u, v, dv/dt and the two helper-backward gradients (src/loss.py:46-76).
         Single GPU: the sums are global, so the same launch also forms the loss values and advances the optimiser's
@@ -1287,9 +1301,6 @@ class Engine:
             # launch and two [L, N] buffers fewer per sub-step; the cycle does not change (1885 steps/s either way): the
             # sweeps start 26 us earlier, next to the test network, whose launch then lasts that much longer -- the first
             # phase of the sub-step is bound by SIMD time, not by this chain.
-            # (pairwise group: the initial penalty is the mean over all PAIRS (u_n - h_m)^2, whose u-gradient is 2 (u_n - mean h) / N)
-            res_A = dict(u=G.u, ref=G.href if G.pair_i else G.h, coef=2.0 * self.alpha / G.Nglob, base=self.pollution, first_only=True)
-            res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False) if G.Nb else None
             e_b = None       # (the boundary sum of squares, a loss value only, is formed by the reduction at the end: _contract(with_bdry))
             # With the reference's pollution (cotangent A = ones + the initial-value term at t_0) sweep A and the helper
             # backward u.backward(ones) are the same adjoint: one launch returns the parameter gradient of A and nabla_x u.
@@ -1299,13 +1310,13 @@ class Engine:
                     self._ode_bwd_multi(sweep_x, G.t, th, *M, want_x=True, want_params=False, adjoint=self.adjoint,
                                      narrow=self._narrow_ok(sweep_x, alone=False, params=False))
                     e_x = self._mark()
-            sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=fused_x), res=res_A)]
+            sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=fused_x), res=self._res_init(G))]
             if joint:
-                sweeps.append(dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b))
+                sweeps.append(dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=self._res_bdry(G)))
             self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=fused_x, want_params=True, x_cot_ones=fused_x, adjoint=self.adjoint,
                              narrow=self._narrow_ok(sweeps, alone=False), prio_drop=self.prio_drop['A'])
             if G.Nb and not joint:
-                sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
+                sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=self._res_bdry(G))]
                 self._ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                                  narrow=self._narrow_ok(sweep_b, alone=False))
             e_A = self._mark()
@@ -1323,9 +1334,7 @@ class Engine:
         # cotangent B = dI/du is a pointwise product of what the two forward passes wrote: sweep B forms it on the fly too
         # (XwOdeBwdJob.res_first_only = 2) and starts right behind the test network: one launch fewer on the critical chain
         # test network -> sweep B -> Adam (0.5063 -> 0.5034 ms per generator sub-step in the same run)
-        res_B = dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob,
-                     weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck))
-        sweep_B = [dict(self._job(G, 'i', None, G.slabB), res=res_B)]
+        sweep_B = [dict(self._job(G, 'i', None, G.slabB), res=self._res_weak(G))]
         self._ode_bwd_multi(sweep_B, G.t, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweep_B, alone=True))
         # the reduction needs nabla_x u (sweep A) and v, not sweep B: it runs behind sweep A on the side stream, next to
@@ -1365,13 +1374,9 @@ class Engine:
             self._reaction(G)
             e_f = self._mark()
         self._join(e_f)
-        res_A = dict(u=G.u, ref=G.href if G.pair_i else G.h, coef=2.0 * self.alpha / G.Nglob, base=self.pollution, first_only=True)
-        res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
-        res_B = dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob,
-                     weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck))
-        sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=True), res=res_A),
-                  dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b),
-                  dict(self._job(G, 'i', None, G.slabB), res=res_B)]
+        sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u], want_x=True), res=self._res_init(G)),
+                  dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=self._res_bdry(G)),
+                  dict(self._job(G, 'i', None, G.slabB), res=self._res_weak(G))]
         self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=True, want_params=True, x_cot_ones=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweeps, alone=bool(getattr(G, 'skip_v', False))))
         G.sumA_ready = False
@@ -1416,12 +1421,8 @@ class Engine:
             e_x = self._mark()
         self._join(e_x)
         self._contract(G, self.adam_u, with_bdry=True)           # -> scal[0] = I, loss values, the optimiser's counter
-        res_M = dict(u=G.u, ref=G.v, coef=G.Vol / G.Nglob / G.L * G.s3_scale, base=G.Vol / G.Nglob,
-                     weak=dict(w=G.w, c=G.c, cp=G.cp, ckappa=G.ck),
-                     merged=dict(ref=G.h, coef=2.0 * self.alpha / G.Nglob, base=self.pollution, scal=self.scal))
-        res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
-        sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u]), res=res_M),
-                  dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
+        sweeps = [dict(self._job(G, 'i', None, G.slabA[:G.ns_u]), res=self._res_merged(G)),
+                  dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=self._res_bdry(G))]
         self._ode_bwd_multi(sweeps, G.t, th, *M, want_x=False, want_params=True, narrow=self._narrow_ok(sweeps, alone=False))
         G.sumA_ready = False
 
@@ -1584,8 +1585,7 @@ class Engine:
             return
         fwd_b = [self._job(G, 'b')]
         self._ode_fwd_multi(fwd_b, G.tb, th, *M, narrow=self._narrow_ok(fwd_b, alone=False, forward=True))
-        res_b = dict(u=G.ub, ref=G.g, coef=2.0 * self.alpha / (G.Nbglob * G.Lb), base=0.0, first_only=False)
-        sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=res_b)]
+        sweep_b = [dict(self._job(G, 'b', None, G.slabA[G.ns_u:]), res=self._res_bdry(G))]
         self._ode_bwd_multi(sweep_b, G.tb, th, *M, want_x=False, want_params=True, adjoint=self.adjoint,
                          narrow=self._narrow_ok(sweep_b, alone=False))
         KN.bdry_partials(G.ub, G.g, self.alpha, G.Nbglob, self.scal, G.work_b)
@@ -1819,9 +1819,7 @@ class Engine:
             KN.dopri5_sweep(part, t, th, H, K, m, want_x, want_params, x_cot_ones=x_cot_ones, stepper=self.dopri5_stepper)
 
     def _u_forward(self, xT, t, start):
-        if self.tiled and not self.dopri5:
-            return KN.tiled_ode_fwd(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, want_Y=False)[0]
-        return KN.u_forward(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, self.config['u_hidden_dim'],
+        return KN.u_forward(xT, t, start, self.theta.data, self.method, self.H, self.K, self.m, self.config['u_hidden_dim'], family=self.stepper,
                             chunk=self.options.dopri5_chunk, max_steps=self.options.dopri5_max_steps, stepper=self.dopri5_stepper)
 
     def predict_group(self, G):

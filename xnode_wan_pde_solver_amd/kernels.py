@@ -207,12 +207,39 @@ def ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True, u=None, Y=None):
         # layout -- four waves of 4 paths per tile, every SIMD busy -- ends sooner (57 against 73 us at 4096 paths x 32 times,
         # 109 against 143 at 64 times; beyond 256 tiles it loses: tools/lone_forward.py).  Same values to the last bit or two.
         arr = (XwOdeFwdJob * 1)()
-        a = arr[0]
-        a.xT, a.start, a.u, a.Y, a.act, a.N, a.act_x_only, a.narrow, a.prio_drop = _p(xT), _p(start), _p(u), 0, 0, N, 0, 1, 0
+        _fwd_job(arr[0], dict(xT=xT, start=start, u=u), d, L, H, narrow=True)
         check(lib.xw_ode_fwd_multi(arr, 1, _p(t), _p(theta), method, L, d, H, K, m, 0, _stream()), 'xw_ode_fwd_multi')
         return u, None
     check(lib.xw_ode_fwd(_p(xT), _p(t), _p(start), _p(theta), method, N, L, d, H, K, m, _p(u), _p(Y), _stream()), 'xw_ode_fwd')
     return u, Y
+
+
+def _launch_dims(jobs, t, theta, H, K):
+    """(L, d, P_u) of a launch over `jobs`, with t and theta checked against them"""
+    L, d = t.shape[0], jobs[0]['xT'].shape[0]
+    P = theta_size(d, H, K)
+    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    return L, d, P
+
+
+def _act(j, store, L, H, N):
+    """a job's activation store, checked, where the family keeps one (store = (method, K, m): the fused and generic paths), else None"""
+    act = j.get('act') if store is not None else None
+    if act is not None:
+        _chk(act, F64, (max(L - 1, 1), ode_act_rows(store[0], H, store[1], store[2]), ode_act_cols(N)), 'act')
+    return act
+
+
+def _fwd_job(a, j, d, L, H, store=None, act_x_only=False, narrow=False, prio_drop=0, hints=True):
+    """check one forward job (dict of xT[d,N], start[N], u[L,N], Y[L,H,N] or None) against the launch's (d, L, H) and fill `a`; returns
+    N.  store: _act's; hints=False: `a` is an XwDopriJob, which has none of act / act_x_only / narrow / prio_drop"""
+    N = j['xT'].shape[1]
+    _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
+    _chk(j.get('Y'), F64, (L, H, N), 'Y')
+    a.xT, a.start, a.u, a.Y, a.N = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y')), N
+    if hints:
+        a.act, a.act_x_only, a.narrow, a.prio_drop = _p(_act(j, store, L, H, N)), 1 if act_x_only else 0, 1 if narrow else 0, int(prio_drop)
+    return N
 
 
 def ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, act_x_only=False, narrow=False, prio_drop=0):
@@ -222,20 +249,10 @@ def ode_fwd_multi(jobs, t, theta, method, H, K, m, zero16=None, act_x_only=False
     narrow: narrow tiles (XwOdeFwdJob.narrow, csrc/xw_ode_n4.h): four waves of 4 paths per 16-path tile -- same outputs, same
     store; for launches that leave SIMDs idle."""
     _need_gpu()
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    L, d, _ = _launch_dims(jobs, t, theta, H, K)
     arr = (XwOdeFwdJob * len(jobs))()
     for a, j in zip(arr, jobs):
-        N = j['xT'].shape[1]
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
-        _chk(j.get('Y'), F64, (L, H, N), 'Y')
-        if j.get('act') is not None:
-            _chk(j['act'], F64, (max(L - 1, 1), ode_act_rows(method, H, K, m), ode_act_cols(N)), 'act')
-        a.xT, a.start, a.u, a.Y, a.act, a.N = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y')), _p(j.get('act')), N
-        a.act_x_only = 1 if act_x_only else 0
-        a.narrow = 1 if narrow else 0
-        a.prio_drop = int(prio_drop)
+        _fwd_job(a, j, d, L, H, (method, K, m), act_x_only, narrow, prio_drop)
     _chk(zero16, F64, (16,), 'zero16')
     check(lib.xw_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _stream()), 'xw_ode_fwd_multi')
 
@@ -270,6 +287,28 @@ def _set_res(a, j, L, N):
         a.res_coef, a.res_base = float(res['coef']), float(res['base'])
 
 
+def _sweep_job(b, j, d, L, H, P, want_x, want_params, x_cot_ones, slabs, with_Y=True, store=None):
+    """check one sweep job (ode_bwd_multi's dict) against the launch's (d, L, H, P) and fill b, an XwOdeBwdJob (dopri5: the .b of its
+    job), residual fields included.  slabs(N): the family's slab count; with_Y=False: dopri5 reverses its record, Y = 0; store: _act's"""
+    N = j['xT'].shape[1]
+    Y = j['Y'] if with_Y else None
+    _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(Y, F64, (L, H, N), 'Y')
+    _chk(j.get('ubar'), F64, (L, N), 'ubar')
+    if want_x and not (x_cot_ones and j.get('gx') is None):
+        _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
+    if want_params:
+        _chk(j['gslab'], F64, (slabs(N), P), 'gslab')
+    b.xT, b.start, b.Y, b.act, b.ubar, b.N = _p(j['xT']), _p(j['start']), _p(Y), _p(_act(j, store, L, H, N)), _p(j.get('ubar')), N
+    b.gx, b.gs, b.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
+    _set_res(b, j, L, N)
+
+
+def _mode_word(want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False, prio_drop=0):
+    """the sweeps' `mode` argument (include/xnwan.h)"""
+    return ((1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | (8 if adjoint else 0)
+            | (16 if narrow else 0) | ((int(prio_drop) & 3) << 5))
+
+
 def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False, prio_drop=0):
     """jobs: list of dicts(xT, start, Y, ubar or None, gx, gs, gslab); ONE launch for all groups.
     res = dict(u[L,N], ref ([N] with first_only, else [L,N]), coef, base, first_only) instead of ubar: the cotangent
@@ -283,32 +322,17 @@ def ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_on
     narrow: narrow tiles (mode bit 4, csrc/xw_ode_n4.h): four waves of 4 paths per 16-path tile instead of one -- for
     launches that leave SIMDs idle; needs every job's activation store (euler, midpoint)."""
     _need_gpu()
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    P = theta_size(d, H, K)
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    L, d, P = _launch_dims(jobs, t, theta, H, K)
     arr = (XwOdeBwdJob * len(jobs))()
     for a, j in zip(arr, jobs):
-        N = j['xT'].shape[1]
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['Y'], F64, (L, H, N), 'Y')
-        _chk(j.get('ubar'), F64, (L, N), 'ubar')
-        if want_x and not (x_cot_ones and j.get('gx') is None):
-            _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
-        if want_params:
-            _chk(j['gslab'], F64, (ode_bwd_slabs(N), P), 'gslab')
-        if j.get('act') is not None:
-            _chk(j['act'], F64, (max(L - 1, 1), ode_act_rows(method, H, K, m), ode_act_cols(N)), 'act')
-        a.xT, a.start, a.Y, a.ubar, a.N = _p(j['xT']), _p(j['start']), _p(j['Y']), _p(j.get('ubar')), N
-        a.act = _p(j.get('act'))
-        a.gx, a.gs, a.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
-        _set_res(a, j, L, N)
+        _sweep_job(a, j, d, L, H, P, want_x, want_params, x_cot_ones, ode_bwd_slabs, store=(method, K, m))
     if x_cot_ones and not (want_x and want_params):
         raise XnwanError('x_cot_ones needs want_x and want_params')
     if x_cot_ones and adjoint:
         raise XnwanError('x_cot_ones is not available with the continuous adjoint')
     if narrow and (adjoint or method > 1 or any(j.get('act') is None for j in jobs)):
         raise XnwanError('narrow-tile sweeps run from the activation store of euler / midpoint (no adjoint=True, no rk4)')
-    mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | (8 if adjoint else 0) | (16 if narrow else 0) | ((int(prio_drop) & 3) << 5)
+    mode = _mode_word(want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop)
     check(lib.xw_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _stream()), 'xw_ode_bwd_multi')
 
 
@@ -336,26 +360,16 @@ def adams_tiled_fwd_multi(jobs, t, theta, H, K, m, zero16=None, prio_drop=0, **_
 
 def _tiled_fwd(jobs, t, theta, method, H, K, m, zero16, prio_drop):
     _need_gpu()
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    L, d, _ = _launch_dims(jobs, t, theta, H, K)
     if method != ADAMS and method not in METHODS.values():
         raise XnwanError("the tiled stepper family runs the fixed-grid methods %s and 'explicit_adams' only" % sorted(METHODS))
     arr = (XwOdeFwdJob * len(jobs))()
     for a, j in zip(arr, jobs):
-        N = j['xT'].shape[1]
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
-        _chk(j.get('Y'), F64, (L, H, N), 'Y')
-        a.xT, a.start, a.u, a.Y, a.act, a.N = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y')), 0, N
-        a.act_x_only, a.narrow, a.prio_drop = 0, 0, int(prio_drop)
+        _fwd_job(a, j, d, L, H, prio_drop=prio_drop)
     _chk(zero16, F64, (16,), 'zero16')
     work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device, method)
-    if method == ADAMS:
-        check(lib.xw_adams_tiled_fwd_multi(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, _p(zero16), _p(work), _stream()),
-              'xw_adams_tiled_fwd_multi')
-    else:
-        check(lib.xw_tiled_ode_fwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, _p(zero16), _p(work), _stream()),
-              'xw_tiled_ode_fwd_multi')
+    entry, sel = ('xw_adams_tiled_fwd_multi', ()) if method == ADAMS else ('xw_tiled_ode_fwd_multi', (method,))   # (Adams takes no method id)
+    check(getattr(lib, entry)(arr, len(jobs), _p(t), _p(theta), *sel, L, d, H, K, m, _p(zero16), _p(work), _stream()), entry)
 
 
 def tiled_ode_bwd_multi(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones=False, adjoint=False, narrow=False,
@@ -377,41 +391,29 @@ def adams_tiled_bwd_multi(jobs, t, theta, H, K, m, want_x, want_params, x_cot_on
     _tiled_bwd(jobs, t, theta, ADAMS, H, K, m, want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop)
 
 
+def _tiled_adjoint_refused(H, K, m=None):      # (m: the single-group call surface names u_layers in place of the reason)
+    return XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
+                      'u_hidden_hidden_dim = %d%s' % (H, K, '): it reverses the steps taken' if m is None else ', u_layers = %d)' % m))
+
+
 def _tiled_bwd(jobs, t, theta, method, H, K, m, want_x, want_params, x_cot_ones, adjoint, narrow, prio_drop):
     _need_gpu()
     if adjoint:
-        raise XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
-                         'u_hidden_hidden_dim = %d): it reverses the steps taken' % (H, K))
+        raise _tiled_adjoint_refused(H, K)
     if narrow:
         raise XnwanError('narrow tiles are not served by the tiled stepper family')
     if x_cot_ones and not (want_x and want_params):
         raise XnwanError('x_cot_ones needs want_x and want_params')
     if not (want_x or want_params):
         raise XnwanError('a sweep produces x outputs, parameter gradients or both')
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    P = theta_size(d, H, K)
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    L, d, P = _launch_dims(jobs, t, theta, H, K)
     arr = (XwOdeBwdJob * len(jobs))()
     for a, j in zip(arr, jobs):
-        N = j['xT'].shape[1]
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['Y'], F64, (L, H, N), 'Y')
-        _chk(j.get('ubar'), F64, (L, N), 'ubar')
-        if want_x and not (x_cot_ones and j.get('gx') is None):
-            _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
-        if want_params:
-            _chk(j['gslab'], F64, (lib.xw_tiled_ode_bwd_slabs(N), P), 'gslab')
-        a.xT, a.start, a.Y, a.ubar, a.N, a.act = _p(j['xT']), _p(j['start']), _p(j['Y']), _p(j.get('ubar')), N, 0
-        a.gx, a.gs, a.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
-        _set_res(a, j, L, N)
-    mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0) | ((int(prio_drop) & 3) << 5)
+        _sweep_job(a, j, d, L, H, P, want_x, want_params, x_cot_ones, lib.xw_tiled_ode_bwd_slabs)
+    mode = _mode_word(want_x, want_params, x_cot_ones, prio_drop=prio_drop)
     work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), t.device, method)
-    if method == ADAMS:
-        check(lib.xw_adams_tiled_bwd_multi(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, _p(work), _stream()),
-              'xw_adams_tiled_bwd_multi')
-    else:
-        check(lib.xw_tiled_ode_bwd_multi(arr, len(jobs), _p(t), _p(theta), method, L, d, H, K, m, mode, _p(work), _stream()),
-              'xw_tiled_ode_bwd_multi')
+    entry, sel = ('xw_adams_tiled_bwd_multi', ()) if method == ADAMS else ('xw_tiled_ode_bwd_multi', (method,))
+    check(getattr(lib, entry)(arr, len(jobs), _p(t), _p(theta), *sel, L, d, H, K, m, mode, _p(work), _stream()), entry)
 
 
 def tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True):
@@ -486,7 +488,7 @@ def ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_par
     P = theta_size(d, H, K)
     _chk(xT, F64, (d, N), 'xT'); _chk(t, F64, (L,), 't'); _chk(start, F64, (N,), 'start'); _chk(theta, F64, (P,), 'theta')
     _chk(Y, F64, (L, H, N), 'Y'); _chk(ubar, F64, (L, N), 'ubar')
-    mode = (1 if want_x else 0) | (2 if want_params else 0) | (8 if adjoint else 0)
+    mode = _mode_word(want_x, want_params, adjoint=adjoint)
     if want_x:
         gx = torch.empty(d, N, dtype=F64, device=xT.device) if gx is None else gx
         gs = torch.empty(N, dtype=F64, device=xT.device) if gs is None else gs
@@ -499,6 +501,23 @@ def ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_par
                          _p(gx if want_x else None), _p(gs if want_x else None), _p(gslab if want_params else None),
                          _stream()), 'xw_ode_bwd')
     return (gx if want_x else None), (gs if want_x else None), (gslab if want_params else None)
+
+
+def family_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True, family=None):
+    """ode_fwd or tiled_ode_fwd (neither routes to the other) for one group and a fixed-grid method, by the family that runs
+    (H, K, m): `family`, or stepper_family's under the default policy"""
+    if (family or stepper_family(H, K, m, method=method)) == 'tiled':       # (H, K: theta's widths -- the network's own on this family)
+        return tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=want_Y)
+    return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=want_Y)
+
+
+def family_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False, adjoint=False, family=None):
+    """ode_bwd / tiled_ode_bwd for one group, chosen as in family_ode_fwd: (gx, gs, gslab)"""
+    if (family or stepper_family(H, K, m, method=method)) != 'tiled':
+        return ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=want_x, want_params=want_params, adjoint=adjoint)
+    if adjoint:
+        raise _tiled_adjoint_refused(H, K, m)
+    return tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=want_x, want_params=want_params)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -595,28 +614,19 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
     chunk, max_steps = int(chunk), int(max_steps)
     if chunk < 1 or max_steps < 1:
         raise XnwanError('dopri5_fwd: chunk and max_steps must be >= 1')
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    dev = t.device
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (theta_size(d, H, K),), 'theta')
-    nj = len(jobs)
+    L, d, _ = _launch_dims(jobs, t, theta, H, K)
+    nj, dev = len(jobs), t.device
     ctl = torch.zeros(nj, lib.xw_dopri5_ctl_size(), dtype=F64, device=dev)
     mirror = torch.empty(ctl.shape, dtype=F64, pin_memory=True)
-    recs = []
-    for j in jobs:
-        N = j['xT'].shape[1]
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['u'], F64, (L, N), 'u')
-        _chk(j.get('Y'), F64, (L, H, N), 'Y')
-        recs.append(Dopri5Record(N, H, int(cap) if cap else 4 * chunk, dev, stepper))
     arr = (XwDopriJob * nj)()
+    recs = [Dopri5Record(_fwd_job(a, j, d, L, H, hints=False), H, int(cap) if cap else 4 * chunk, dev, stepper) for a, j in zip(arr, jobs)]
     work = _dopri5_tiled_work(False, d, H, K, m, [r.N for r in recs], dev) if takes_work else None
     tail = (_p(work), _stream()) if takes_work else (_stream(),)
 
-    def fill():
-        for i, (a, j, r) in enumerate(zip(arr, jobs, recs)):
-            a.xT, a.start, a.u, a.Y = _p(j['xT']), _p(j['start']), _p(j['u']), _p(j.get('Y'))
+    def fill():                            # (the record's fields: again after a record has grown)
+        for i, (a, r) in enumerate(zip(arr, recs)):
             a.rec_y, a.rec_t, a.rec_h, a.fbuf = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.fbuf)
-            a.ctl, a.work, a.N, a.cap = _p(ctl[i]), _p(r.work), r.N, r.cap
+            a.ctl, a.work, a.cap = _p(ctl[i]), _p(r.work), r.cap
     args = (_p(t), _p(theta), L, d, H, K, m, int(Hn), float(rtol), float(atol))
     fill()
     check(getattr(lib, init)(arr, nj, *args, *tail), init)
@@ -649,13 +659,11 @@ def dopri5_fwd(jobs, t, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, 
     return recs
 
 
-def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS, stepper='vector'):
-    """u[L,N] of one group with any served solver: ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
+def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_steps=DOPRI5_MAX_STEPS, stepper='vector', family=None):
+    """u[L,N] of one group with any served solver: family_ode_fwd for the fixed-grid methods, dopri5_fwd (one job) for DOPRI5.
     Hn: the network's u_hidden_dim (dopri5's RMS norms); stepper: dopri5's implementation (DOPRI5_STEPPERS)"""
     if method != DOPRI5:
-        if stepper_family(H, K, m, method=method) == 'tiled':
-            return tiled_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
-        return ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False)[0]
+        return family_ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=False, family=family)[0]
     u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)
     dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps, stepper=stepper)
     return u
@@ -672,27 +680,16 @@ def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False,
         raise XnwanError('dopri5_sweep: 1 .. %d jobs per call, got %d' % (DOPRI5_MAXJOBS, len(jobs)))
     if x_cot_ones and not (want_x and want_params):
         raise XnwanError('x_cot_ones needs want_x and want_params')
-    L = t.shape[0]
-    d = jobs[0]['xT'].shape[0]
-    P = theta_size(d, H, K)
-    _chk(t, F64, (L,), 't'); _chk(theta, F64, (P,), 'theta')
+    L, d, P = _launch_dims(jobs, t, theta, H, K)
     arr = (XwDopriSweepJob * len(jobs))()
     for a, j in zip(arr, jobs):
         N = j['xT'].shape[1]
         r = j['rec']
         if r.N != N or r.H != H:
             raise XnwanError('dopri5_sweep: the record is for N = %d, H = %d' % (r.N, r.H))
-        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j.get('ubar'), F64, (L, N), 'ubar')
-        if want_x and not (x_cot_ones and j.get('gx') is None):
-            _chk(j['gx'], F64, (d, N), 'gx'); _chk(j['gs'], F64, (N,), 'gs')
-        if want_params:
-            _chk(j['gslab'], F64, (ode_bwd_slabs(N), P), 'gslab')
-        b = a.b
-        b.xT, b.start, b.Y, b.act, b.ubar, b.N = _p(j['xT']), _p(j['start']), 0, 0, _p(j.get('ubar')), N
-        b.gx, b.gs, b.gslab = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('gslab'))
-        _set_res(b, j, L, N)
+        _sweep_job(a.b, j, d, L, H, P, want_x, want_params, x_cot_ones, ode_bwd_slabs, with_Y=False)
         a.rec_y, a.rec_t, a.rec_h, a.ctl = _p(r.rec_y), _p(r.rec_t), _p(r.rec_h), _p(r.ctl)
-    mode = (1 if want_x else 0) | (2 if want_params else 0) | (4 if x_cot_ones else 0)
+    mode = _mode_word(want_x, want_params, x_cot_ones)
     work = _dopri5_tiled_work(True, d, H, K, m, [a.b.N for a in arr], t.device) if takes_work else None
     tail = (_p(work), _stream()) if takes_work else (_stream(),)
     check(getattr(lib, sweep)(arr, len(jobs), _p(t), _p(theta), L, d, H, K, m, mode, *tail), sweep)

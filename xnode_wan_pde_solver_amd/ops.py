@@ -28,10 +28,7 @@ def xnode_forward(X: torch.Tensor, start: torch.Tensor, blob: torch.Tensor, meth
     xT = X[:, 0, 1:].detach().to(F64).t().contiguous()
     t = X[0, :, 0].detach().to(F64).contiguous()
     s = start.detach().to(F64).reshape(-1).contiguous()
-    if KN.stepper_family(H, K, m, method=method) == 'tiled':    # (H, K: the blob's widths -- the network's own on this family)
-        u, Y = KN.tiled_ode_fwd(xT, t, s, blob, method, H, K, m, want_Y=keep)
-    else:
-        u, Y = KN.ode_fwd(xT, t, s, blob, method, H, K, m, want_Y=keep)
+    u, Y = KN.family_ode_fwd(xT, t, s, blob, method, H, K, m, want_Y=keep)
     return [u.t().unsqueeze(2).contiguous(), Y if keep else torch.empty(0, dtype=F64, device=u.device)]
 
 
@@ -49,13 +46,7 @@ def xnode_backward(gu: torch.Tensor, X: torch.Tensor, start: torch.Tensor, Y: to
     t = X[0, :, 0].detach().to(F64).contiguous()
     s = start.detach().to(F64).reshape(-1).contiguous()
     ubar = gu.squeeze(2).t().contiguous().to(F64)
-    if KN.stepper_family(H, K, m, method=method) == 'tiled':
-        if adjoint:
-            raise KN.XnwanError('adjoint=True (the continuous adjoint) is not served by the tiled stepper family (u_hidden_dim = %d, '
-                                'u_hidden_hidden_dim = %d, u_layers = %d)' % (H, K, m))
-        gx, gs, slab = KN.tiled_ode_bwd(xT, t, s, blob, Y, ubar, method, H, K, m, want_x=True, want_params=want_params)
-    else:
-        gx, gs, slab = KN.ode_bwd(xT, t, s, blob, Y, ubar, method, H, K, m, want_x=True, want_params=want_params, adjoint=adjoint)
+    gx, gs, slab = KN.family_ode_bwd(xT, t, s, blob, Y, ubar, method, H, K, m, want_x=True, want_params=want_params, adjoint=adjoint)
     gp = KN.slab_sum(slab) if want_params else torch.zeros(0, dtype=F64, device=gu.device)
     return [gx.t().contiguous(), gs, gp]
 
