@@ -15,6 +15,8 @@ starts at a multiple of ALIGN bytes (what torch's allocator gives a tensor of it
                     test and pinned from both sides.  An AssertionError names the buffer and the first offending index.
     workspaces(KN)  context manager: kernels.tiled_ode_work and kernels._dopri5_tiled_work (torch.empty outside every arena)
                     return views of this arena, of the same size, PATTERN-filled and guarded; the arena keeps them until check()
+    dopri5_records(KN)  context manager: the tensors of kernels.Dopri5Record (rec_y, rec_t, rec_h, fbuf, work; at construction and
+                    in grow) are views of this arena, of the same shapes, PATTERN-filled and guarded, kept until check()
 """
 import contextlib
 from unittest import mock
@@ -96,6 +98,34 @@ class Arena:
             return self.out(dopri(*a, **kw).numel(), name='dopri5_tiled_work')
 
         with mock.patch.object(KN, 'tiled_ode_work', tiled_ode_work), mock.patch.object(KN, '_dopri5_tiled_work', dopri5_tiled_work):
+            yield self
+
+    @contextlib.contextmanager
+    def dopri5_records(self, KN):
+        """kernels.Dopri5Record keeps its tensors in this arena: rec_y, rec_t, rec_h, fbuf and work are views of the shapes the class
+        itself gives them (torch.empty outside every arena), PATTERN-filled and guarded, at construction and again in grow(), which
+        carries the first n_acc + 1 grid points over as the class does.  The arena keeps every generation until check(), so a store
+        into a record that has been replaced still lands in memory the test owns.  Not covered: the per-launch controller rows and
+        their page-locked mirror (torch.zeros / torch.empty inside kernels.dopri5_fwd) stay outside the arena."""
+        arena, base = self, KN.Dopri5Record
+
+        class GuardedRecord(base):
+            FIELDS = ('rec_y', 'rec_t', 'rec_h', 'fbuf', 'work')
+
+            def __init__(rec, *a, **kw):
+                super().__init__(*a, **kw)
+                for k in rec.FIELDS:
+                    setattr(rec, k, arena.out(getattr(rec, k).shape, name='dopri5.' + k))
+
+            def grow(rec, cap, n_acc):
+                super().grow(cap, n_acc)                    # (new tensors outside the arena, the kept grid points copied in)
+                for k, keep in (('rec_y', n_acc + 1), ('rec_t', n_acc + 1), ('rec_h', n_acc)):
+                    new = getattr(rec, k)
+                    v = arena.out(new.shape, name='dopri5.%s(cap %d)' % (k, cap))
+                    v[:keep].copy_(new[:keep])
+                    setattr(rec, k, v)
+
+        with mock.patch.object(KN, 'Dopri5Record', GuardedRecord):
             yield self
 
     # ---- the checks ---------------------------------------------------------------------------------------------------------

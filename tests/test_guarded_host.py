@@ -129,3 +129,56 @@ def test_workspace_patch_hands_out_guarded_views_of_the_same_size():
     c.f64[e + 407] = 1.0                                        # ... but not past its end
     with pytest.raises(AssertionError, match='1 doubles behind the end of tiled_ode_work'):
         arena.check()
+
+
+def test_record_patch_keeps_the_dopri5_record_in_the_arena():
+    class KN:                                                   # (a stand-in for the kernels module: the record class alone)
+        class Dopri5Record:
+            def __init__(self, N, H, cap, dev, stepper='vector'):
+                self.N, self.H, self.cap = N, H, cap
+                self.rec_y = torch.empty(cap + 1, H, N, dtype=F64, device=dev)
+                self.rec_t = torch.empty(cap + 1, dtype=F64, device=dev)
+                self.rec_h = torch.empty(max(cap, 1), dtype=F64, device=dev)
+                self.fbuf = torch.empty(2, H, N, dtype=F64, device=dev)
+                self.work = torch.empty(2 * ((N + 63) // 64), dtype=F64, device=dev)
+
+            def grow(self, cap, n_acc):
+                y, tt, h = self.rec_y, self.rec_t, self.rec_h
+                self.rec_y = torch.empty(cap + 1, self.H, self.N, dtype=F64, device=y.device)
+                self.rec_t = torch.empty(cap + 1, dtype=F64, device=y.device)
+                self.rec_h = torch.empty(cap, dtype=F64, device=y.device)
+                self.rec_y[:n_acc + 1].copy_(y[:n_acc + 1])
+                self.rec_t[:n_acc + 1].copy_(tt[:n_acc + 1])
+                self.rec_h[:n_acc].copy_(h[:n_acc])
+                self.cap = cap
+
+    orig = KN.Dopri5Record
+    arena = G.Arena('cpu')
+    with arena.dopri5_records(KN):
+        r = KN.Dopri5Record(65, 3, 2, 'cpu')
+        assert isinstance(r, orig)
+        first = {k: getattr(r, k) for k in ('rec_y', 'rec_t', 'rec_h', 'fbuf', 'work')}
+        assert {k: tuple(v.shape) for k, v in first.items()} == {'rec_y': (3, 3, 65), 'rec_t': (3,), 'rec_h': (2,), 'fbuf': (2, 3, 65),
+                                                                 'work': (4,)}
+        for v in first.values():
+            arena._where(v)                                     # (a view of this arena)
+            assert bool((v.view(torch.int64) == G.PATTERN).all())
+        r.rec_y[:2] = 1.0                                       # one accepted step, as the kernels would leave it
+        r.rec_t[:2] = torch.tensor([0.0, 0.5], dtype=F64)
+        r.rec_h[:1] = 0.5
+        r.grow(5, 1)
+        assert r.cap == 5 and tuple(r.rec_y.shape) == (6, 3, 65) and tuple(r.rec_t.shape) == (6,) and tuple(r.rec_h.shape) == (5,)
+        assert r.fbuf is first['fbuf'] and r.work is first['work'] and r.rec_y is not first['rec_y']
+        assert float(r.rec_y[:2].min()) == 1.0 and r.rec_t[:2].tolist() == [0.0, 0.5] and r.rec_h[:1].tolist() == [0.5]
+    assert KN.Dopri5Record is orig                              # (restored on exit)
+    arena.check(written=[r.rec_y[:2], r.rec_t[:2], r.rec_h[:1], first['rec_y'][:2]],
+                untouched=[r.rec_y[2:], r.rec_t[2:], r.rec_h[1:], r.fbuf, r.work, first['rec_y'][2:]])
+    c, e, _ = arena._where(first['rec_y'])                      # a store behind the end of the record that was replaced
+    c.f64[e + first['rec_y'].numel()] = 1.0
+    with pytest.raises(AssertionError, match=r'1 doubles behind the end of dopri5\.rec_y#'):
+        arena.check()
+    c.raw[e + first['rec_y'].numel()] = G.PATTERN
+    c, e, _ = arena._where(r.rec_h)                             # ... and one behind the grown step-size record
+    c.f64[e + 5] = 0.25
+    with pytest.raises(AssertionError, match=r'1 doubles behind the end of dopri5\.rec_h\(cap 5\)'):
+        arena.check()
