@@ -28,7 +28,31 @@ class loss:
         X.grad.data.zero_()
         return g
 
+    def _I_single_slice(self, u_s, v3, X, XV):
+        """I on the single-slice group at T0 of a list domain, where u_net returns [N, 1] (nets.XNODE.forward) against v [N, 1, 1]:
+        the reference squeezes every unit axis, so [N] factors meet [N, 1] factors and the u dphi/dt, b and (c u + f) phi terms
+        become [N, N] tables over all PAIRS of paths, summed over both axes.  Written after the oracle's weak_I_shaped (the weak
+        form on the reference's shapes) and u_net_shaped (the [N, 1] return); the engine serves the same sums as `pair_i`."""
+        d = self.setup['dim']
+        N, L = u_s.shape[0], u_s.shape[1]
+        w = self.func_w(XV).to(self.device)
+        phi3 = v3 * w.unsqueeze(2)
+        du = self._input_grad(u_s, torch.ones_like(u_s), X)
+        dphi = self._input_grad(phi3, torch.ones_like(phi3), XV)
+        uq, pq, cq = u_s.squeeze(), phi3.squeeze(), self.c.squeeze()
+        s1 = self.V * (u_s[:, -1].squeeze() * v3[:, -1].squeeze() - self.h * v3[:, 0].squeeze()) / N
+        s2 = self.V * (uq.detach() * dphi[:, :, 0]) / N / L
+        s3 = 0
+        for i in range(d):
+            for j in range(d):
+                s3 = s3 + self.a[i, j] * dphi[:, :, i + 1] * du[:, :, j + 1]
+            s3 = s3 + self.b[i] * pq.detach() * du[:, :, i + 1]
+        s3 = s3 + cq * uq * pq + self.f * pq
+        return torch.sum(s1 - torch.sum(s2 - (self.V / N / L) * s3, 1), 0)
+
     def I(self, y_output_u, y_output_v, X, XV):
+        if y_output_u.dim() == 2:
+            return self._I_single_slice(y_output_u, y_output_v, X, XV)
         d = self.setup['dim']
         N, L = y_output_u.shape[0], y_output_u.shape[1]
         u, v = y_output_u.squeeze(2), y_output_v.squeeze(2)

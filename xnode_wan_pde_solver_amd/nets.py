@@ -124,6 +124,17 @@ def _v_slots(d, W, Wc):
 # ----------------------------------------------------------------------------------------------------------------------
 # autograd bridges (compat path for user code; the training loop calls the kernels directly)
 # ----------------------------------------------------------------------------------------------------------------------
+def _route(net, gflat, L):
+    """the flat gradient of u_theta as one piece per parameter -- None for the field's (ODE_rhs) when the forward pass took no
+    step (L == 1: a single time slice, at T0 or on the boundary).  The field is then no part of the function: the reference never
+    puts it in the graph, its .grad stays None, and torch's Adam skips it -- no step counted, no moment decayed.  A tensor of
+    zeros would count a step and, from the second sub-iteration on, move the field by its decaying moments."""
+    gp = net.blob.split(gflat)
+    if L == 1:
+        gp = [None if n.startswith('ODE_rhs.') else g for n, g in zip(net.blob.names, gp)]
+    return gp
+
+
 class _OdeFn(torch.autograd.Function):
     """u_net(X).backward(): both directions are the registered operators xnwan::xnode_forward / xnode_backward (ops.py);
     this Function only routes the flat parameter gradient to the module's parameters (views of the blob)."""
@@ -143,8 +154,12 @@ class _OdeFn(torch.autograd.Function):
         net = ctx.net
         X, start, Y = ctx.saved_tensors
         want_p = any(ctx.needs_input_grad[3:])
+        # The sweep always runs with its parameter part, also when every parameter is frozen: the sweep without it is another
+        # kernel instantiation, whose d/dx can differ from this one's in the last bit ((20, 10, 8), rk4: one float64 ulp,
+        # profiles/r22_module_surface.md) -- and the gradient X receives must not depend on which other gradients were asked for.
+        # Freezing ALL of u_theta is rare on this path (the loss's helper backward passes run with the parameters live).
         gx, gs, gflat = torch.ops.xnwan.xnode_backward(gu.contiguous(), X, start, Y, net.blob.data, net.method, net.kdims[0],
-                                                       net.kdims[1], net.num_layers, bool(net.adjoint), want_p)
+                                                       net.kdims[1], net.num_layers, bool(net.adjoint), True)
         gX = None
         if ctx.needs_input_grad[0]:
             # nabla_x u is deposited at time index 0 (the model reads x from slice 0 only, src/model.py:99); the time
@@ -152,7 +167,7 @@ class _OdeFn(torch.autograd.Function):
             gX = torch.zeros(X.shape, dtype=ctx.x_dtype, device=gu.device)
             gX[:, 0, 1:] = gx.to(ctx.x_dtype)
         gS = gs.view(ctx.s_shape).to(ctx.s_dtype) if ctx.needs_input_grad[1] else None
-        gp = net.blob.split(gflat) if want_p else [None] * len(net.blob.params)
+        gp = _route(net, gflat, X.shape[1]) if want_p else [None] * len(net.blob.params)
         return (gX, gS, None) + tuple(gp)
 
 
@@ -196,7 +211,7 @@ class _Dopri5Fn(torch.autograd.Function):
             gX = torch.zeros((N, t.shape[0], d + 1), dtype=ctx.x_dtype, device=gu.device)
             gX[:, 0, 1:] = gx.t().to(ctx.x_dtype)
         gS = gs.view(ctx.s_shape).to(ctx.s_dtype) if ctx.needs_input_grad[1] else None
-        gp = net.blob.split(KN.slab_sum(gslab)) if want_p else [None] * len(net.blob.params)
+        gp = _route(net, KN.slab_sum(gslab), t.shape[0]) if want_p else [None] * len(net.blob.params)
         return (gX, gS, None) + tuple(gp)
 
 

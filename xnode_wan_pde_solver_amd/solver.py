@@ -48,7 +48,9 @@ def func_eval(X, BX, setup, y_output_u, func_a, func_b, func_c, func_h, func_f, 
     b[d,N,L], c[N,L,1] (attached to y_output_u).  Kept for user code; the engine itself never builds a[d,d,N,L]."""
     d = setup['dim']
     h, f, g = func_h(X[:, 0, :]), func_f(X), func_g(BX)
-    c = func_c(X, y_output_u)
+    # (tabulated where X lives, like h, f, g, a, b: u_net's output is on the GPU also for a host sample, and a c(u, t, x) that
+    #  reads X cannot mix the two; .to() is differentiable, and the loss moves c to the device again)
+    c = func_c(X, y_output_u.to(X.device))
     a = torch.empty(d, d, X.shape[0], X.shape[1])
     for i, j in product(range(d), repeat=2):
         a[i, j] = func_a(X, i, j)
@@ -150,11 +152,29 @@ class FusedAdam:
             p.grad = None
 
     def step(self):
-        g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in self.blob.params])
+        # the gradient in the blob's own layout: an embedded network's parameters are strided views of their containers, a field
+        # without hidden layer leaves its slot empty -- the padding receives a zero gradient and stays zero
+        g = torch.zeros_like(self.blob.data)
+        for view, p in zip(self.blob.split(g), self.blob.params):
+            if p.grad is not None:
+                view.copy_(p.grad)
+        lag = {}
+        if 'lag' in self.state:
+            # u_theta: the field's parameters count their own steps (engine.Engine.__init__).  While none of them has a gradient --
+            # no group of this sub-iteration has taken an ODE step yet, nets._route -- torch's Adam skips them: no step counted, no
+            # moment decayed (xw_adam lag / skip).  Any other parameter without gradient is updated with a zero gradient.
+            field = [p.grad is None for n, p in zip(self.blob.names, self.blob.params) if n.startswith('ODE_rhs.')]
+            lag = dict(lag=self.state['lag'], lag_range=(self.blob.slots[6][0], self.blob.slots[-2][0]), skip=all(field))
         _adam_kernel(self.blob.data, None, self.state['m'], self.state['v'], self.state['step'],
-                     self.param_groups[0]['lr'], gextraA=g.contiguous())
+                     self.param_groups[0]['lr'], gextraA=g, **lag)
         if self.on_step is not None:
             self.on_step()
+
+    def steps(self):
+        """Adam's step count per parameter (named_parameters() order), as torch.optim.Adam keeps it in state[p]['step']"""
+        step = int(self.state['step'].item())
+        lag = int(self.state['lag'].item()) if 'lag' in self.state else 0
+        return [step - lag if n.startswith('ODE_rhs.') else step for n in self.blob.names]
 
     def state_dict(self):
         sd = {'m': self.state['m'].clone(), 'v': self.state['v'].clone(), 'step': int(self.state['step'].item()), 'lr': self.lr}
