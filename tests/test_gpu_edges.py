@@ -24,7 +24,7 @@ Regions pinned as untouched (from the code):
   tiled test network              the record's columns of the points past N L in its last 16-point tile (only valid points store);
                                   vt, gxv, gtv where not requested are not passed at all
   test-network MFMA containers    nothing: the record's padding columns ARE written (every lane of the ragged last tile stores a copy
-                                  of the last valid point into a slot of its own, csrc/xw_disc.hip k_disc_fwd): all of it is checked
+                                  of the last valid point into a slot of its own, csrc/xw_disc_fwd.hip k_disc_fwd): all of it is checked
   fused containers                nothing: the activation store's padding columns ARE written (padding paths hold copies and have
                                   slots of their own, csrc/xw_ode.hip act_store).  At (64, 16) every double row of the store is
                                   checked as written; at (20, 10) the partial 4-row block (K mod 4 = 2) leaves slots unused inside the

@@ -1,5 +1,5 @@
 """Every compiled test-network kernel against the oracle, inside a guarded arena: the cases of tests/testnet_inventory.py -- one per
-instantiation of k_disc_fwd, k_disc_rec and k_disc_bwd (csrc/xw_disc.hip) at the smallest shape that selects it, k_disc_xproj, the
+instantiation of k_disc_fwd, k_disc_rec and k_disc_bwd (csrc/xw_disc_fwd.hip, xw_disc_rec.hip, xw_disc_bwd.hip) at the smallest shape that selects it, k_disc_xproj, the
 tiled family's kernel per row-tile count, the generic pair at five widths, and the edges of the selection rules (d = 24 | 25,
 52 | 53, 46 | 47, 94 | 95, 62 | 63, 126).  tests/test_testnet_inventory_host.py: the cases reach exactly the kernels the library holds.
 

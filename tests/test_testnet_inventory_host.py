@@ -23,7 +23,7 @@ def test_every_compiled_testnet_kernel_is_reached_and_every_case_lands_on_one():
     assert not have - set(want) - set(TI.UNREACHED), 'compiled, but no case runs them: %s' % sorted(have - set(want), key=repr)
     assert not set(want) - have, 'forms that land on a kernel the library does not hold: %s' % sorted(
         ((k, [TI.cid(c) for c in want[k]]) for k in set(want) - have), key=repr)
-    # what the library holds today (a change detector beside the set equality): 48 / 24 / 4 / 1 of csrc/xw_disc.hip, 4 + 4 of the
+    # what the library holds today (a change detector beside the set equality): 48 / 24 / 4 / 1 of csrc/xw_disc_fwd.hip, _rec, _bwd, 4 + 4 of the
     # tiled family, the generic pair
     assert collections.Counter(k[0] for k in have) == {'fwd': 48, 'rec': 24, 'bwd': 4, 'xproj': 1, 't_fwd': 4, 't_bwd': 4,
                                                        'g_fwd': 1, 'g_bwd': 1}
@@ -33,6 +33,10 @@ def test_every_compiled_testnet_kernel_is_reached_and_every_case_lands_on_one():
     assert {k for k in have if k[0] == 'rec'} == {('rec', W, 0, ng, ts) for W in TI.CONTAINERS for ng in (1, 2, 3) for ts in (False, True)}
     assert {k for k in have if k[0] == 'bwd'} == {('bwd', 50, 9, ctg, p, not p) for ctg in (1, 2) for p in (False, True)}
     assert {k[1] for k in have if k[0] == 't_fwd'} == {k[1] for k in have if k[0] == 't_bwd'} == {4, 8, 12, 16}
+    # all instantiations of one container kernel sit in one code object (what else a translation unit holds moves code generation)
+    objs = TI.code_objects(_lib.LIB_PATH)
+    for family in ('fwd', 'rec', 'bwd'):
+        assert sum(1 for obj in objs if any(k[0] == family for k in obj)) == 1, family
 
 
 def test_cases_are_what_the_inventory_says():

@@ -1,8 +1,9 @@
 """The test network's compiled kernels, and the launches that reach them -- TEST INFRASTRUCTURE ONLY (imported like
 tests/stepper_inventory.py, whose loader of tools/isa_same.py it reuses).  CPU only.
 
-csrc/xw_disc.hip compiles into one kernel per container width, record, schedule and input-layer plan (k_disc_fwd), per width, input
-groups and path-group form (k_disc_rec), per cotangent groups and output (k_disc_bwd), and k_disc_xproj; csrc/xw_disc_tiled.hip into
+csrc/xw_disc_fwd.hip, xw_disc_rec.hip and xw_disc_bwd.hip compile into one kernel per container width, record, schedule and input-layer
+plan (k_disc_fwd), per width, input groups and path-group form (k_disc_rec), per cotangent groups and output (k_disc_bwd), and
+k_disc_xproj -- all instantiations of one template in one code object (code_objects) --; csrc/xw_disc_tiled.hip into
 one forward and one reverse kernel per row-tile count; csrc/xw_generic.hip holds the generic pair.  Two views of that set:
 
     compiled(path)   what a built libxnwan.so holds: the kernel symbols of its gfx950 code objects, names only (parse_kernel)
@@ -63,18 +64,30 @@ def parse_kernel(text):
     return (family,) + args
 
 
-def compiled(path):
-    """the set of test-network kernel tuples in `path` (a libxnwan.so or one object).  Reads the function symbols of .text
-    (llvm-objdump -t --demangle) of every gfx950 code object; never an instruction."""
-    found = set()
+def code_objects(path):
+    """the test-network kernel tuples of `path` (a libxnwan.so or one object), one set per gfx950 code object that holds any.  Reads the
+    function symbols of .text (llvm-objdump -t --demangle); never an instruction."""
+    out = []
     with tempfile.TemporaryDirectory() as tmp:
         for co in isa_same.bundles(path, tmp):
+            found = set()
             for line in isa_same.run(isa_same.LLVM + '/llvm-objdump', '-t', '--demangle', co).splitlines():
                 if re.match(r'^[0-9a-f]+ \S+\s+F \.text\s', line):
                     k = parse_kernel(line)
                     if k is not None:
                         assert k not in found, 'compiled twice: %r' % (k,)
                         found.add(k)
+            if found:
+                out.append(found)
+    return out
+
+
+def compiled(path):
+    """the set of test-network kernel tuples in `path`, over all its code objects"""
+    found = set()
+    for obj in code_objects(path):
+        assert not found & obj, 'compiled twice: %r' % sorted(found & obj, key=repr)
+        found |= obj
     return found
 
 

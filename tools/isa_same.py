@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of two builds the same?  Runs on the CPU (llvm-objdump only).
 usage: tools/isa_same.py A B      A, B: two directories of objects (compared by file name) or two libxnwan.so
+       tools/isa_same.py --by-kernel A B      for two builds that partition their kernels into objects differently (see below)
 Per object: the gfx950 bundle (llvm-objdump --offloading) byte for byte; where the bytes differ, per kernel symbol the instruction
 text without addresses, .vgpr_count / .agpr_count / .sgpr_count and the scratch and LDS size of the notes.  One line per object:
-'identical' or 'N kernels differ' and their names; exit status 1 on any difference."""
+'identical' or 'N kernels differ' and their names; exit status 1 on any difference.
+--by-kernel: every kernel symbol of A against the same symbol of B, in whichever object (or code object of a library) each sits:
+the instruction text up to the symbol's size -- what the disassembler prints for the alignment padding behind a kernel's last
+instruction depends on what follows it --, the register counts, scratch and LDS.  Lists the kernels that differ, the kernels
+present on one side only, and the objects whose gfx950 bundles are byte-identical; exit status 1 on any of the first two."""
 import glob
 import os
 import re
@@ -45,6 +50,55 @@ def kernels(co):
     return out
 
 
+def kernels_sized(co):
+    """{kernel symbol: (instruction lines below the symbol's end, {note key: value})}: by address, from the symbol table"""
+    lines = []
+    for line in run(LLVM + '/llvm-objdump', '-d', co).splitlines():
+        m = re.match(r'^\t(.*?)\s*// ([0-9A-F]+): ', line)
+        if m:
+            lines.append((int(m.group(2), 16), m.group(1).strip()))
+    span = {}
+    for m in re.finditer(r'^\s*\d+: ([0-9a-f]+)\s+(\d+) FUNC\s+\S+\s+\S+\s+\S+ (\S+)$', run(LLVM + '/llvm-readelf', '-sW', co), re.M):
+        span[m.group(3)] = (int(m.group(1), 16), int(m.group(1), 16) + int(m.group(2)))
+    return {k: ([t for a, t in lines if span[k][0] <= a < span[k][1]] if k in span else None, notes) for k, (_, notes) in kernels(co).items()}
+
+
+def objects(path):
+    return [os.path.join(path, n) for n in sorted(os.listdir(path)) if n.endswith('.o')] if os.path.isdir(path) else [path]
+
+
+def by_kernel(a, b):
+    """compare per kernel symbol over all code objects of A and of B"""
+    with tempfile.TemporaryDirectory() as tmp:
+        side, raw = [], []
+        for root in (a, b):
+            ks, bytes_of = {}, {}
+            for obj in objects(root):
+                cos = bundles(obj, tmp)
+                bytes_of[os.path.basename(obj)] = [open(c, 'rb').read() for c in cos]
+                for i, c in enumerate(cos):
+                    for k, v in kernels_sized(c).items():
+                        ks[k] = v + (os.path.basename(obj) + ('[%d]' % i if len(cos) > 1 else ''),)
+            side.append(ks)
+            raw.append(bytes_of)
+    ka, kb = side
+    both = sorted(set(ka) & set(kb))
+    bad = [k for k in both if ka[k][:2] != kb[k][:2] or ka[k][0] is None]
+    moved = [k for k in both if ka[k][2] != kb[k][2]]
+    print('%d kernels in A, %d in B, %d in both: %d identical (instructions to the symbol size, registers, scratch, LDS), %d differ; '
+          '%d sit in an object of another name' % (len(ka), len(kb), len(both), len(both) - len(bad), len(bad), len(moved)))
+    for k in bad:
+        print('differs   %s   (%s | %s)' % (k, ka[k][2], kb[k][2]))
+    for name, x, y in (('A', ka, kb), ('B', kb, ka)):
+        for k in sorted(set(x) - set(y)):
+            print('only in %s %s   (%s)' % (name, k, x[k][2]))
+    if os.path.isdir(a):
+        for n in sorted(set(raw[0]) | set(raw[1])):
+            print('%-28s %s' % (n, 'only in A' if n not in raw[1] else 'only in B' if n not in raw[0] else
+                                'bundle byte-identical' if raw[0][n] == raw[1][n] else 'bundle bytes differ'))
+    return 1 if bad or set(ka) ^ set(kb) else 0
+
+
 def compare(a, b, tmp):
     ca, cb = bundles(a, tmp), bundles(b, tmp)
     if len(ca) != len(cb):
@@ -80,6 +134,8 @@ def main(a, b):
 
 
 if __name__ == '__main__':
+    if len(sys.argv) == 4 and sys.argv[1] == '--by-kernel':
+        sys.exit(by_kernel(sys.argv[2], sys.argv[3]))
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Print a table of per-kernel register / LDS / scratch usage (hipcc -Rpass-analysis=kernel-resource-usage)."""
 import re, subprocess, sys
-srcs = sys.argv[1:] or ['xw_ode.hip', 'xw_disc.hip', 'xw_weak.hip']
+srcs = sys.argv[1:] or ['xw_ode.hip', 'xw_disc_fwd.hip', 'xw_disc_rec.hip', 'xw_disc_bwd.hip', 'xw_weak.hip']
 for f in srcs:
     out = subprocess.run(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I../../include',
                           *(['-mllvm', '-amdgpu-mfma-vgpr-form=1'] if f == 'xw_ode.hip' else []), '-Rpass-analysis=kernel-resource-usage', '-c', f, '-o', '/dev/null'], capture_output=True, text=True).stderr

@@ -69,6 +69,18 @@ __host__ __device__ inline VOff v_offsets(int d, int W) {
   o.total = p;
   return o;
 }
+// v_phi: point -> (time, path): path mode p = l N + n, point mode (tpp) p = n.  For the per-point families (xw_generic.hip,
+// xw_disc_tiled.hip); the containers locate a lane of a tile (xw_disc_core.h)
+__device__ __forceinline__ void xw_locate_pt(long p, int N, const double* tf, const double* tpp, double& t, int& nidx) {
+  if (tpp != nullptr) {
+    nidx = (int)p;
+    t = tpp[p];
+  } else {
+    const int l = (int)(p / N);
+    nidx = (int)(p - (long)l * N);
+    t = tf[l];
+  }
+}
 
 // ---- explicitly GLOBAL loads / stores ---------------------------------------------------------------------------------
 // A pointer that went through an `asm volatile("" : "+s"(p))` (laundered, so that address arithmetic stays where it is

@@ -19,24 +19,13 @@
 // matrix unit (A from LDS, B straight from the record), one 16 x 16 tile of dVh per wave at a time, added into the block's
 // own slab.  No float atomics: every slab entry has one writer and a fixed order.
 #include <hip/hip_runtime.h>
-#include "xw_common.h"
+#include "xw_disc_core.h"   // (the slab count of the reverse kernels: one function for every family)
 #include "../../include/xnwan.h"
 
 #define XWD_MAX_W 256
 #define XWD_MAX_Q 32
 
 namespace {
-
-__device__ __forceinline__ void dt_locate(long p, int N, const double* tf, const double* tpp, double& t, int& nidx) {
-  if (tpp != nullptr) {
-    nidx = (int)p;
-    t = tpp[p];
-  } else {
-    const int l = (int)(p / N);
-    nidx = (int)(p - (long)l * N);
-    t = tf[l];
-  }
-}
 
 // record index of (row, point p)
 __device__ __forceinline__ long dt_rec(long p, int rows, int row) { return ((p >> 4) * rows + row) * 16 + (p & 15); }
@@ -63,7 +52,7 @@ __global__ void __launch_bounds__(256, 1) k_dt_fwd(const double* __restrict__ xT
     const long p = valid ? raw : P - 1;
     double t;
     int nidx;
-    dt_locate(p, N, tf, tpp, t, nidx);
+    xw_locate_pt(p, N, tf, tpp, t, nidx);
     const bool grad = gxv != nullptr && tile * 8 < ngrad;          // (wave-uniform)
     d4 a[NT], b[NT];
     // input layer: B rows = (t, x_0 .. x_{d-1}) for the values, e_0 for the tangents
@@ -293,7 +282,7 @@ __global__ void __launch_bounds__(256, 1) k_dt_bwd(const double* __restrict__ xT
             if (pk < P && col <= d) {
               double tk;
               int nk;
-              dt_locate(pk, N, tf, tpp, tk, nk);
+              xw_locate_pt(pk, N, tf, tpp, tk, nk);
               val = col == 0 ? tk : xw_ld_g(xT + (long)(col - 1) * N + nk);
             }
             bf[ks] = val;
@@ -324,11 +313,6 @@ __global__ void __launch_bounds__(256, 1) k_dt_bwd(const double* __restrict__ xT
     slab[o.Vo + tid] += accO;
   }
   if (tid == 0) slab[o.Vob] += accOb;
-}
-
-int dt_slabs(long P) {
-  const long nsuper = (P + 63) / 64;
-  return (int)(nsuper < 512 ? nsuper : 512);
 }
 
 }  // namespace
@@ -373,7 +357,7 @@ extern "C" int xw_disc_tiled_bwd(const double* xT, const double* t, const double
   if (!xw_disc_tiled_ok(d, W, q)) return XW_E_DIMS;
   if (!act) return XW_E_DIMS;                                  // (from the record only)
   const long P = (long)N * L;
-  const int nslab = dt_slabs(P);
+  const int nslab = bwd_blocks(P);
   hipStream_t s = (hipStream_t)stream;
   XWD_DISPATCH(k_dt_bwd, (unsigned)nslab, xT, t, tpp, phi, vbar, N, L, d, W, q, act, gslab);
   return xw_launch_status();

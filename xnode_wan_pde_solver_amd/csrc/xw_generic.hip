@@ -1,10 +1,10 @@
 // xw_generic.hip -- the GENERIC-WIDTH path of both networks: any u_hidden_dim <= 64, u_hidden_hidden_dim <= 16, v_hidden_dim <= 128.
 //
-// The reference accepts any widths (src/model.py:30-43, 62-85, 130-138).  The MFMA kernels of xw_ode.hip / xw_disc.hip are built
+// The reference accepts any widths (src/model.py:30-43, 62-85, 130-138).  The MFMA kernels of xw_ode.hip / xw_disc_*.hip are built
 // around the shipped shapes -- hidden-hidden activations are ONE 16-row tile, the test network's dVh maps four row tiles onto the
 // four waves of a block -- and serve (20,10), (32,12) and W = 50, 64 (narrower networks run exactly inside them, zero-padded).
 // Everything wider lands here: the same entry points (xw_ode_fwd_multi, xw_ode_bwd_multi, xw_disc_fwd, xw_disc_bwd: the dispatch
-// is in xw_ode_abi.hip / xw_disc.hip), the same arguments, layouts and results, as plain per-path / per-point code on the vector
+// is in xw_ode_abi.hip / xw_disc_fwd.hip, xw_disc_bwd.hip), the same arguments, layouts and results, as plain per-path / per-point code on the vector
 // ALU.  A SLOW path by construction -- one lane per path (stepper) or per point (test network), weights read through the scalar
 // cache, no matrix instructions: two to three orders of magnitude below the MFMA kernels (profiles/r05_generic_widths.txt) --
 // whose job is that a legal reference configuration trains instead of raising.
@@ -184,18 +184,6 @@ __global__ void __launch_bounds__(64) kg_ode_bwd(XwOdeBwdJob job, const double* 
 }
 
 // ---- v_phi ---------------------------------------------------------------------------------------------------------------------
-// point -> (time, path): path mode p = l N + n, point mode (tpp) p = n
-__device__ __forceinline__ void locate_pt(long p, int N, const double* tf, const double* tpp, double& t, int& nidx) {
-  if (tpp != nullptr) {
-    nidx = (int)p;
-    t = tpp[p];
-  } else {
-    const int l = (int)(p / N);
-    nidx = (int)(p - (long)l * N);
-    t = tf[l];
-  }
-}
-
 __global__ void __launch_bounds__(64) kg_disc_fwd(const double* __restrict__ xT, const double* __restrict__ tf,
                                                    const double* __restrict__ tpp, const double* __restrict__ ph, int N, int L,
                                                    int d, int W, int q, double* __restrict__ v, double* __restrict__ vt,
@@ -207,7 +195,7 @@ __global__ void __launch_bounds__(64) kg_disc_fwd(const double* __restrict__ xT,
   const VOff o = v_offsets(d, W);
   double t;
   int nidx;
-  locate_pt(p, N, tf, tpp, t, nidx);
+  xw_locate_pt(p, N, tf, tpp, t, nidx);
   double a[GW], ad[GW], nw[GW], nd[GW];
   unsigned long long mk[GQ][(GW + 63) / 64];
   const bool grad = gxv != nullptr && p < ngrad;
@@ -319,7 +307,7 @@ __global__ void __launch_bounds__(64) kg_disc_bwd(const double* __restrict__ xT,
     const long p = valid ? raw : P - 1;
     double t;
     int nidx;
-    locate_pt(p, N, tf, tpp, t, nidx);
+    xw_locate_pt(p, N, tf, tpp, t, nidx);
     const double vb = valid ? (vbar ? vbar[p] : 1.0) : 0.0;
     double dls[(GQ + 1) * GW];                                   // dls[j * GW + k]: cotangent of a_j[k] (j = q: of the last pre-activation)
     double* dq = dls + q * GW;

@@ -1045,7 +1045,7 @@ class Engine:
                         gxv=G.gxv, gtv=G.gtv, ngrad=G.N, max_blocks=blocks, act=act)
         else:
             # (the input layer's spatial columns do not move along a vertical path: applied once per path by a small launch in
-            #  front, csrc/xw_disc.hip k_disc_xproj -- the main launch then loads its row of that table instead of x)
+            #  front, csrc/xw_disc_fwd.hip k_disc_xproj -- the main launch then loads its row of that table instead of x)
             #  -- unless the group's table is still that of this phi and this sample: _xproj_state)
             xp = None
             if 'xproj' in G._lazy:
