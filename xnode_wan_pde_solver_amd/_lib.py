@@ -34,6 +34,11 @@ class XwPathsJob(ctypes.Structure):       # include/xnwan.h: one ragged group of
                 ('last_only', c_int)]
 
 
+class XwPathsDopriJob(ctypes.Structure):  # include/xnwan_eval.h: one group of xw_paths_dopri5_fwd (a step controller per path)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('t_in', c_vp), ('t_end', c_vp), ('u', c_vp), ('status', c_vp), ('n_acc', c_vp),
+                ('n_att', c_vp), ('Y', c_vp), ('rec', c_vp), ('fin', c_vp), ('N', c_int), ('cap', c_int)]
+
+
 class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
     _fields_ = [('xT', c_vp), ('start', c_vp), ('u', c_vp), ('Y', c_vp), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp),
                 ('fbuf', c_vp), ('ctl', c_vp), ('work', c_vp), ('N', c_int), ('cap', c_int)]
@@ -154,6 +159,13 @@ SIGNATURES = {
     'xw_comm_destroy': [c_vp],
 }
 
+# the extension header include/xnwan_eval.h (include/xnwan.h and SIGNATURES above are frozen at ABI_VERSION): same conventions
+EVAL_SIGNATURES = {
+    'xw_paths_dopri5_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_dopri5_fwd': [ctypes.POINTER(XwPathsDopriJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_int,
+                            c_int, c_f64p, c_vp],
+}
+
 ERRORS = {-1: 'XW_E_DIMS: network widths/depths not among the compiled kernel instantiations',
           -2: 'XW_E_ARG: null pointer, non-positive size or bad enum',
           -3: 'XW_E_WORKSPACE: workspace too small',
@@ -174,7 +186,7 @@ def _load():
     # living in the other (every launch then fails with hipErrorNoDevice: build() followed by smoke() in ONE process did)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

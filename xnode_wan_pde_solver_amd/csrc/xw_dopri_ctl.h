@@ -1,7 +1,8 @@
 // xw_dopri_ctl.h -- what the two implementations of solver 'dopri5' share (xw_dopri.hip: the field per path on the vector ALU;
 // xw_tdopri.hip: the field per 16-path tile on the matrix pipe): the controller slots, the Dormand-Prince tableau, the dense
 // output, the job pack of a launch, the per-job ticket reduction, the step controller (ctl_init1 / ctl_init2 / ctl_attempt: what the
-// lane that job_sum returns true on does with the totals) and the host side's job checks.  What stays with each implementation is
+// lane that job_sum returns true on does with the totals) and the host side's job checks.  xw_tdopri_paths.hip, a controller per
+// PATH, takes the tableau, the dense output and the controller's formulas by value (ctl_h0 / ctl_first_dt / ctl_next_dt).  What stays with each implementation is
 // how a block or a tile forms its partial sums and where its vectors live.  Library-internal; included INSIDE an anonymous
 // namespace, after xw_generic_cot.h and after a gsum64(double) (the sum over the wave) has been declared.
 #pragma once
@@ -91,12 +92,29 @@ __device__ __forceinline__ bool job_sum(double (&val)[NV], double* __restrict__ 
   return true;
 }
 
+// ---- the controller's formulas, by value: what ctl_init1 / ctl_init2 / ctl_attempt below do with a job's norms, and kq_paths
+// (xw_tdopri_paths.hip) with the norms of a lane's own path ---------------------------------------------------------------------
+// torchdiffeq _select_initial_step: h0 from d0 = ||y0 / scale||, d1 = ||f0 / scale||
+__device__ __forceinline__ double ctl_h0(double d0, double d1) { return (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1; }
+// ... and the first step from d1, d2 = ||(f(t0 + h0, y0 + h0 f0) - f0) / scale|| / h0
+// (ctl_init2 keeps its own text of these two lines: routed through this function its kernels compile to other instructions)
+__device__ __forceinline__ double ctl_first_dt(double d1, double d2, double h0) {
+  const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
+  return fmin(100 * h0, h1);
+}
+// torchdiffeq _optimal_step_size, order 5: the step size after an attempt over dt with error ratio `ratio` (not NaN)
+__device__ __forceinline__ double ctl_next_dt(double dt, double ratio) {
+  if (ratio == 0.0) return dt * DP_IFACTOR;
+  const double dfac = ratio < 1.0 ? 1.0 : DP_DFACTOR;
+  return dt * fmin(DP_IFACTOR, fmax(DP_SAFETY / pow(ratio, 1.0 / 5), dfac));
+}
+
 // ---- the step controller: lane 0 of the last block of a job, with the job's totals ---------------------------------------------
 // torchdiffeq _select_initial_step, first half: d0 = ||y0 / scale||, d1 = ||f0 / scale|| (acc: their squared sums), h0
 __device__ __forceinline__ void ctl_init1(const double (&acc)[2], int N, int Hn, double* c) {
   const double cnt = (double)N * Hn;
   const double d0 = sqrt(acc[0] / cnt), d1 = sqrt(acc[1] / cnt);
-  c[C_H0] = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+  c[C_H0] = ctl_h0(d0, d1);
   c[C_D1] = d1;
 }
 
@@ -137,13 +155,7 @@ __device__ __forceinline__ void ctl_attempt(double acc, int N, int Hn, double t0
     return;
   }
   const bool accept = ratio <= 1.0;
-  double dtn;
-  if (ratio == 0.0) {
-    dtn = dt * DP_IFACTOR;
-  } else {
-    const double dfac = ratio < 1.0 ? 1.0 : DP_DFACTOR;
-    dtn = dt * fmin(DP_IFACTOR, fmax(DP_SAFETY / pow(ratio, 1.0 / 5), dfac));
-  }
+  const double dtn = ctl_next_dt(dt, ratio);
   double tn = t0;
   if (accept) {
     if (!room) {

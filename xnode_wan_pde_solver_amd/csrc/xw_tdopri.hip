@@ -35,31 +35,7 @@ namespace {
 __device__ __forceinline__ double gsum64(double x) { return xw_sum_over_g(xw_sum_over_n(x)); }   // sum over the wave
 
 #include "xw_dopri_ctl.h"
-
-// the per-tile workspace: the family's TileWork, then the stages k_0 .. k_6 (sweep: and their cotangents) as H-vectors
-struct TdWork {
-  TileWork w;
-  long k, total;
-};
-__host__ __device__ inline TdWork td_work(int sweep, int d, int H, int K, int m) {
-  TdWork q;
-  q.w = tile_work(sweep, d, H, K, m);
-  q.k = q.w.total;
-  q.total = q.w.total + 16L * H * (sweep ? 14 : 7);
-  return q;
-}
-
-// a = y + dt sum_{q < st} a_{st,q} k_q: the input of stage st (st = 0: y itself)
-__device__ void stage_input(int H, int st, double dt, const double* y, const double* kk, double* a) {
-  double c[6];
-  for (int q = 0; q < st; ++q) c[q] = DP_A[st][q] * dt;
-  for (int e = lane_id(); e < 16 * H; e += 64) {
-    double acc = 0.0;
-    for (int q = 0; q < st; ++q) acc = fma(kk[16L * H * q + e], c[q], acc);
-    a[e] = y[e] + acc;
-  }
-  sync_tile();
-}
+#include "xw_tdopri_blocks.h"   // the per-tile workspace (td_work) and the input of a stage (stage_input)
 
 __global__ void __launch_bounds__(64) kq_init1(const Jobs<XwDopriJob> J, const double* __restrict__ tf, const double* __restrict__ theta,
                                                int L, int d, int H, int K, int m, int Hn, double rtol, double atol,

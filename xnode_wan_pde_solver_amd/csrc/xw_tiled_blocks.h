@@ -1,7 +1,7 @@
 // xw_tiled_blocks.h -- the building blocks of the tiled stepper family: the per-tile workspace; the tile products, field, VJP, lift
 // and combinations; and the sequences its kernels share -- the fixed-grid step, the rk4 reverse, the output block, the cotangent on
-// u of a time index, the sweeps' prologue and tail.  Used by xw_tiled.hip, xw_tiled_paths.hip and
-// xw_tdopri.hip; kt_ode_bwd alone keeps its own text of the sweep pieces (xw_tiled.hip says why).  Library-internal; included INSIDE an anonymous namespace, after xw_common.h, xnwan.h and
+// u of a time index, the sweeps' prologue and tail.  Used by xw_tiled.hip, xw_tiled_paths.hip,
+// xw_tdopri.hip and xw_tdopri_paths.hip; kt_ode_bwd alone keeps its own text of the sweep pieces (xw_tiled.hip says why).  Library-internal; included INSIDE an anonymous namespace, after xw_common.h, xnwan.h and
 // xw_generic_cot.h (cot_u; the host's check of a sweep job, sweep_job_ok, is there too).
 #pragma once
 

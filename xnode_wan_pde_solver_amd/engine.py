@@ -1843,8 +1843,10 @@ class Engine:
         widths, whichever family trains; fixed-grid schemes only; EngineOptions.eval_chunk_paths paths per launch."""
         from . import evalpaths
         if self.method not in KN.METHODS.values():
-            raise XnwanError("predict_paths: solver %r is not served -- per-path time grids run the fixed-grid schemes %s only"
-                             % (self.config['solver'], sorted(KN.METHODS)))
+            raise XnwanError("predict_paths: solver %r is not served -- per-path time grids run the fixed-grid schemes %s only%s"
+                             % (self.config['solver'], sorted(KN.METHODS),
+                                " (dopri5's per-path step controller, kernels.paths_dopri5_fwd, gives one output time per path: "
+                                "solver.evaluate; several output times per path are not built)" if self.method == KN.DOPRI5 else ''))
         with torch.no_grad():
             Xd = X.detach()
             if Xd.dim() != 3 or Xd.shape[2] != 1 + self.d:

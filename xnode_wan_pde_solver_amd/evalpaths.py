@@ -7,7 +7,11 @@ tiles homogeneous in their step count (sort_by_steps), the chunked launch (paths
 
 A point (t, x) is entered at (t_in, x) -- the domain class's `entry` rule: T0 with the start value h, or the moving boundary
 with g -- and integrated over n = max(1, ceil((t - t_in) / ((T - T0) / n_sub))) equal steps that end exactly at t; t == t_in takes
-none.  No gradients, no collective calls, no random numbers."""
+none.  No gradients, no collective calls, no random numbers.
+
+Solver 'dopri5' has no grid to pack: kernels.paths_dopri5_fwd (csrc/xw_tdopri_paths.hip) runs a step controller per path from
+t_in to t -- one odeint call of the reference per point -- and paths_dopri5 chunks it, with one read-back of the status words per
+chunk; evaluate_points takes it with tol = (rtol, atol)."""
 import torch
 
 from . import kernels as KN
@@ -69,12 +73,44 @@ def paths_forward(xT, tT, start, nstep, theta, method, H, K, m, last_only=False,
     return torch.cat(parts, -1)
 
 
-def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+def paths_dopri5(xT, t_in, t_end, start, theta, H, K, m, Hn, rtol, atol, max_steps=KN.DOPRI5_MAX_STEPS, max_attempts=None,
+                 chunk=EVAL_CHUNK_PATHS):
+    """kernels.paths_dopri5_fwd on N paths, at most `chunk` of them per launch, ONE read-back of the status words per chunk:
+    dict(u [N], fin [2, N] on the device; status, n_acc, n_att [N] int32 on the host).  Nothing is raised for a status."""
+    N, dev = xT.shape[1], xT.device
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    u = torch.empty(N, dtype=F64, device=dev)
+    fin = torch.empty(2, N, dtype=F64, device=dev)
+    words = torch.empty(3, N, dtype=torch.int32)
+    for lo in range(0, N, chunk):
+        n = min(lo + chunk, N) - lo
+        whole = n == N
+        w = torch.empty(3, n, dtype=torch.int32, device=dev)
+        job = dict(xT=xT if whole else xT[:, lo:lo + n].contiguous(), start=start[lo:lo + n], t_in=t_in[lo:lo + n],
+                   t_end=t_end[lo:lo + n], u=u[lo:lo + n], status=w[0], n_acc=w[1], n_att=w[2],
+                   fin=fin if whole else torch.empty(2, n, dtype=F64, device=dev))
+        KN.paths_dopri5_fwd([job], theta, H, K, m, Hn, rtol=rtol, atol=atol, max_steps=max_steps, max_attempts=max_attempts)
+        if not whole:
+            fin[:, lo:lo + n] = job['fin']
+        words[:, lo:lo + n] = w.cpu()                        # (the chunk's one read-back: waits for its launch)
+    return dict(u=u, fin=fin, status=words[0], n_acc=words[1], n_att=words[2])
+
+
+def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS, tol=None,
+                    Hn=None, max_steps=KN.DOPRI5_MAX_STEPS):
     """u_theta at points [M, 1 + d] (time first; host or device, float32 or float64) -> u [M] float64 on `device`.
-    domain: the domain class or an instance (only its classmethod `entry` is used: nothing is constructed, nothing is drawn)."""
-    if solver in REFUSED_SOLVERS:
+    domain: the domain class or an instance (only its classmethod `entry` is used: nothing is constructed, nothing is drawn).
+    tol = (rtol, atol) with solver 'dopri5': every point is one adaptive solve of its own from its entry to t, a step controller
+    per path (paths_dopri5; Hn: the network's u_hidden_dim, H unless given; max_steps: accepted steps per path); n_sub has no
+    meaning there and must be None.  A path whose controller ends with a status raises XnwanError."""
+    adaptive = solver == 'dopri5' and tol is not None
+    if solver in REFUSED_SOLVERS and not adaptive:
         raise XnwanError("evaluate(): solver %r is not served -- per-path time grids run the fixed-grid schemes %s only (no "
                          "per-path step controller or multistep history is built)" % (solver, sorted(KN.METHODS)))
+    if adaptive and n_sub is not None:
+        raise XnwanError("evaluate(): n_sub = %r with solver 'dopri5' -- every point's step sizes are its controller's (rtol, atol); "
+                         "a number of steps over [T0, T] has no meaning there" % (n_sub,))
     entry = getattr(domain, 'entry', None)
     if entry is None:
         name = getattr(domain, '__name__', type(domain).__name__)
@@ -82,7 +118,7 @@ def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H
                          'starts, and with which start value, is the domain\'s to say' % name)
     d, T0, T = setup['dim'], setup['T0'], setup['T']
     n_sub = setup['N_t'] if n_sub is None else n_sub
-    if n_sub < 1:
+    if not adaptive and n_sub < 1:
         raise XnwanError('evaluate(): n_sub = %r, at least one step over [T0, T]' % (n_sub,))
     if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 1 + d):
         raise XnwanError('evaluate(): points must be a tensor [M, 1 + d] = [M, %d], time first' % (1 + d))
@@ -97,12 +133,28 @@ def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H
             i = int(early.nonzero()[0])
             raise XnwanError('evaluate(): %d points lie before their entry time (t >= t_in is the limit; first: point %d, t = %r, '
                              't_in = %r)' % (int(early.sum()), i, float(t[i]), float(t_in[i])))
-        n = step_counts(t, t_in, T0, T, n_sub)
         first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
         if bool(at_T0.all()):
             s = h(first).reshape(-1).double()
         else:                               # (both callables on every point, then a select: the batched form of h(x0) / g(x0))
             s = torch.where(at_T0, h(first).reshape(-1).double(), g(first.unsqueeze(1)).reshape(-1).double())
+        if adaptive:
+            # sorted by the length of the interval -- what a path's step count grows with; the count itself is the controller's --
+            # so that the 16 paths of a tile, which walk together until the last of them is done, need about the same rounds
+            order, inverse = sort_by_steps(t - t_in)
+            r = paths_dopri5(pts[order, 1:].t().contiguous().to(device), t_in[order].contiguous().to(device),
+                             t[order].contiguous().to(device), s[order].contiguous().to(device), theta, H, K, m,
+                             H if Hn is None else Hn, float(tol[0]), float(tol[1]), max_steps=max_steps, chunk=chunk)
+            bad = (r['status'] != 0).nonzero().view(-1)
+            if bad.numel():
+                i = int(order[bad.to(order.device)].min())       # the first such point, as the caller numbers them
+                k = int(inverse[i])
+                fin = r['fin'][:, k].tolist()
+                msg = KN.dopri5_status_message(int(r['status'][k]), [fin[0], fin[1], int(r['n_acc'][k]), int(r['n_att'][k])], max_steps)
+                raise XnwanError('evaluate(): %d of %d points did not reach their time (first: point %d, t = %r, t_in = %r): %s'
+                                 % (bad.numel(), t.numel(), i, float(t[i]), float(t_in[i]), msg))
+            return r['u'][inverse.to(device)]
+        n = step_counts(t, t_in, T0, T, n_sub)
         order, inverse = sort_by_steps(n)
         tT = pack_grids(t[order], t_in[order], n[order]).to(device)
         u = paths_forward(pts[order, 1:].t().contiguous().to(device), tT, s[order].contiguous().to(device),

@@ -5,7 +5,7 @@ Conventions (include/xnwan.h): point arrays are time-major [L, N]; coordinates a
 """
 import torch
 
-from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob
+from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 DOPRI5 = 3                                 # solver 'dopri5' (adaptive, dopri5_fwd / dopri5_sweep below): not a fixed-grid method id
@@ -667,6 +667,48 @@ def u_forward(xT, t, start, theta, method, H, K, m, Hn, chunk=DOPRI5_CHUNK, max_
     u = torch.empty(t.shape[0], xT.shape[1], dtype=F64, device=xT.device)
     dopri5_fwd([dict(xT=xT, start=start, u=u)], t, theta, H, K, m, Hn, chunk=chunk, max_steps=max_steps, stepper=stepper)
     return u
+
+
+def paths_dopri5_fwd(jobs, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATOL, max_steps=DOPRI5_MAX_STEPS, max_attempts=None):
+    """solver 'dopri5' with a step controller PER PATH (csrc/xw_tdopri_paths.hip, include/xnwan_eval.h): every path is one odeint
+    call of the reference on the one-path group with the sample times [t_in, t_end], the whole integration of a 16-path tile in one
+    launch.  job = dict(xT[d,N], start[N], t_in[N], t_end[N] >= t_in, u[N], status[N], n_acc[N], n_att[N] (int32), optional Y[H,N]
+    -- the state at t_end --, rec[cap,2,N] -- t0 and dt of each accepted step below cap -- and fin[2,N] -- t0 and dt of every
+    controller when it stopped); theta at the widths (H, K), the generic layout; Hn: the network's u_hidden_dim (the RMS norms
+    divide by it).  max_steps: accepted steps per path; max_attempts: rounds of a tile, 2 max_steps unless given -- the kernel's
+    hard bound.  A path that ends at either gets status XW_DOPRI_STEPS (2); nothing is read back here, nothing raised for a status:
+    the launch can be captured (the caller reads status, dopri5_status_message words it)."""
+    _need_gpu()
+    max_steps = int(max_steps)
+    max_attempts = 2 * max_steps if max_attempts is None else int(max_attempts)
+    if max_steps < 1 or max_attempts < 1:
+        raise XnwanError('paths_dopri5_fwd: max_steps and max_attempts must be >= 1')
+    d = jobs[0]['xT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    arr = (XwPathsDopriJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start')
+        _chk(j['t_in'], F64, (N,), 't_in'); _chk(j['t_end'], F64, (N,), 't_end'); _chk(j['u'], F64, (N,), 'u')
+        for k in ('status', 'n_acc', 'n_att'):
+            if j.get(k) is None:
+                raise XnwanError('paths_dopri5_fwd: a job needs %s[N] (int32)' % k)
+            _chk(j[k], torch.int32, (N,), k)
+        rec = j.get('rec')
+        cap = 0
+        if rec is not None:
+            if rec.dim() != 3:
+                raise XnwanError('rec must have shape (cap, 2, %d), got %s' % (N, tuple(rec.shape)))
+            cap = rec.shape[0]
+            _chk(rec, F64, (cap, 2, N), 'rec')
+        _chk(j.get('Y'), F64, (H, N), 'Y'); _chk(j.get('fin'), F64, (2, N), 'fin')
+        a.xT, a.start, a.t_in, a.t_end, a.u = _p(j['xT']), _p(j['start']), _p(j['t_in']), _p(j['t_end']), _p(j['u'])
+        a.status, a.n_acc, a.n_att = _p(j['status']), _p(j['n_acc']), _p(j['n_att'])
+        a.Y, a.rec, a.fin, a.N, a.cap = _p(j.get('Y')), _p(rec), _p(j.get('fin')), N, cap
+    # (xw_paths_dopri5_work is the tiled dopri5 forward's workspace, xw_tdopri5_work(0, ...): one allocation helper for both)
+    work = _dopri5_tiled_work(False, d, H, K, m, [a.N for a in arr], theta.device)
+    check(lib.xw_paths_dopri5_fwd(arr, len(jobs), _p(theta), d, H, K, m, int(Hn), float(rtol), float(atol), max_steps, max_attempts,
+                                  _p(work), _stream()), 'xw_paths_dopri5_fwd')
 
 
 def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False, stepper='vector'):

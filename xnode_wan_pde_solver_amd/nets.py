@@ -319,21 +319,26 @@ class XNODE(nn.Module):
             return self.h(first).reshape(-1).double()
         return self.g(first.unsqueeze(1)).reshape(-1).double()
 
-    def evaluate(self, points, n_sub=None, chunk=None):
+    def evaluate(self, points, n_sub=None, chunk=None, max_steps=None):
         """u_theta at scattered space-time points [M, 1 + d] (time first; host or device) -> u [M] on the network's device: every
         point is integrated from its own entry (the domain class's `entry` rule: T0 with h, or the moving boundary with g) over
         n = max(1, ceil((t - t_in) / ((T - T0) / n_sub))) equal steps ending exactly at t, n_sub = setup['N_t'] by default --
-        one launch chain for the whole cloud (evalpaths.evaluate_points).  No gradients.  Refused: t < t_in, the solvers
-        'dopri5' and 'explicit_adams', a domain class without `entry`.  chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS)."""
+        one launch chain for the whole cloud (evalpaths.evaluate_points).  Solver 'dopri5': every point is one adaptive solve from
+        its entry to t with a step controller of its own (rtol, atol of this module, the RMS norms over u_hidden_dim entries: one
+        odeint call of the reference per point); n_sub must be None; max_steps: accepted steps per point (self.dopri5_max_steps),
+        a point that does not get there raises.  At the blob's widths whichever stepper trains.  No gradients.  Refused: t < t_in,
+        the solver 'explicit_adams', a domain class without `entry`.  chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS)."""
         from . import evalpaths
         if self.blob is None:
             raise XnwanError('XNODE.bind(device) has not been called')
         self.blob.check_alias()
         dev = self.blob.data.device
+        adaptive = dict(tol=(self.rtol, self.atol), Hn=self.hidden_dim,
+                        max_steps=self.dopri5_max_steps if max_steps is None else max_steps) if self.method == KN.DOPRI5 else {}
         with torch.cuda.device(dev):
             return evalpaths.evaluate_points(points, n_sub, self.setup, self.domain, self.solver, self.h, self.g, self.blob.data,
                                              self.method, self.kdims[0], self.kdims[1], self.num_layers, dev,
-                                             chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk)
+                                             chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk, **adaptive)
 
     def forward(self, inputs, starts_at_T0=None):
         """starts_at_T0 (optional): the caller knows where the paths start -- True: at T0 (start values h), False: on the

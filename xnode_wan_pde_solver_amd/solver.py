@@ -279,8 +279,10 @@ class NODE_WAN_solver:
     def evaluate(self, points, n_sub=None):
         """the trained solution at scattered space-time points [M, 1 + d] (time first; host or device) -> u [M] on the solver's
         device, in one launch chain (XNODE.evaluate: a time grid per point, setup['N_t'] steps over [T0, T] unless n_sub says
-        otherwise).  No gradients, no collective calls (every rank evaluates what it is given), no random numbers drawn."""
-        return self.u_net.module.evaluate(points, n_sub, chunk=self.options.eval_chunk_paths)
+        otherwise; solver 'dopri5': one adaptive solve per point, a step controller per path, at most
+        EngineOptions.dopri5_max_steps accepted steps each, n_sub must be None).  No gradients, no collective calls (every rank
+        evaluates what it is given), no random numbers drawn."""
+        return self.u_net.module.evaluate(points, n_sub, chunk=self.options.eval_chunk_paths, max_steps=self.options.dopri5_max_steps)
 
     # --------------------------------------------------------------------------------------------------------------
     def _new_domain(self):
