@@ -1,14 +1,16 @@
 """The fused stepper's compiled kernels, and the launch forms that reach them -- TEST INFRASTRUCTURE ONLY (imported like
 tests/guarded.py).  CPU only.
 
-The fused stepper (csrc/xw_ode.hip with xw_ode_mfma4.h, xw_ode_mfma16.h, xw_ode_n4.h) is compiled once per container, depth, method
-and launch form: every instantiation is its own machine code with its own schedule.  Two views of that set:
+The fused stepper (csrc/xw_ode_fwd.h and xw_ode.hip over xw_ode_core.h, the form headers xw_ode_mfma4.h / xw_ode_mfma16.h
+and the narrow tiles of xw_ode_n4.h) is compiled once per container, depth, method and launch form: every instantiation is its own
+machine code with its own schedule.  Two views of that set:
 
     compiled(path)      what a built libxnwan.so (or a directory of xw_ode_*.o) holds: the kernel symbols of its gfx950 code objects,
-                        names only, parsed to tuples (parse_kernel)
+                        names only, parsed to tuples (parse_kernel); code_objects(path): the same, one set per code object
     reaches(H, K, m, method, form)
-                        what a launch lands on: a restatement of the dispatch in launch_fwd, launch_fwd_narrow, the two launch_bwd
-                        and xw_ode_bwd_recomp_w, in terms of what a caller of kernels.ode_fwd_multi / ode_bwd_multi passes
+                        what a launch lands on: a restatement of the selection in csrc/xw_ode_select.h (choose_fwd, choose_sweep,
+                        recomp_slot) and of the tables its slots index (xw_ode_fwd.h, xw_ode.hip), in terms of what a caller
+                        of kernels.ode_fwd_multi / ode_bwd_multi passes
 
 tests/test_stepper_inventory_host.py asserts that the two are the same set; tests/test_gpu_stepper_inventory.py runs every form of
 every case against the oracle, so a new instantiation cannot appear without a case that runs it.
@@ -32,8 +34,8 @@ _spec.loader.exec_module(isa_same)
 
 METHODS = ('euler', 'midpoint', 'rk4')                       # method ids 0, 1, 2 (kernels.METHODS)
 ODE_WIDTHS = ((20, 10), (32, 12), (64, 16))                  # kernels.ODE_WIDTHS (asserted by the host test)
-NARROW_WIDTHS = ((20, 10), (32, 12))                         # the 4x4x4 containers: the only ones with narrow tiles (xw_ode_mfma4.h)
-DEPTHS = tuple(range(1, 11))                                 # XW_ODE_DISPATCH.  Nothing reads the macro: what binds DEPTHS (and the
+NARROW_WIDTHS = ((20, 10), (32, 12))                         # the 4x4x4 containers: the only ones with narrow tiles (XW_ODE_HAS_NARROW)
+DEPTHS = tuple(range(1, 11))                                 # XW_ODE_DEPTHS of xw_ode_select.h.  Nothing reads it: what binds DEPTHS (and the
                                                              # two tuples above, beyond the host test's comparison with `kernels`) to the
                                                              # build is the set equality reaches == compiled of the host test
 
@@ -56,20 +58,32 @@ def parse_kernel(text):
     return (family,) + args
 
 
-def compiled(path):
-    """the set of stepper kernel tuples in `path`: a libxnwan.so, one object, or a directory of xw_ode_*.o.  Reads the function
-    symbols of .text (llvm-objdump -t --demangle) of every gfx950 code object; never an instruction."""
+def code_objects(path):
+    """the stepper kernel tuples of `path` (a libxnwan.so, one object, or a directory of xw_ode_*.o), one set per gfx950 code object
+    that holds any.  Reads the function symbols of .text (llvm-objdump -t --demangle); never an instruction."""
     files = sorted(os.path.join(path, n) for n in os.listdir(path) if re.match(r'xw_ode_.*\.o$', n)) if os.path.isdir(path) else [path]
-    found = set()
+    out = []
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
             for co in isa_same.bundles(f, tmp):
+                found = set()
                 for line in isa_same.run(isa_same.LLVM + '/llvm-objdump', '-t', '--demangle', co).splitlines():
                     if re.match(r'^[0-9a-f]+ \S+\s+F \.text\s', line):
                         k = parse_kernel(line)
                         if k is not None:
                             assert k not in found, 'compiled twice: %r' % (k,)
                             found.add(k)
+                if found:
+                    out.append(found)
+    return out
+
+
+def compiled(path):
+    """the set of stepper kernel tuples in `path`, over all its code objects"""
+    found = set()
+    for obj in code_objects(path):
+        assert not found & obj, 'compiled twice: %r' % sorted(found & obj, key=repr)
+        found |= obj
     return found
 
 
@@ -121,14 +135,15 @@ def reaches(H, K, m, method, form):
         raise KeyError((H, K, m, method, form))
     mid = METHODS.index(method)
     if form in FWD_FORMS:
-        # launch_fwd: sel = method * 3 + (0 no store, 1 full, 2 x-only); launch_fwd_narrow takes the same sel when jobs.narrow
+        # choose_fwd: method * 3 + (0 no store, 1 full, 2 x-only) of the seven forward kinds; the narrow-tile kernel of the same kind
+        # when the jobs ask for narrow tiles
         spec = FWD_FORMS[form]
         return ('fwd_n4' if spec['narrow'] else 'fwd', H, K, m, mid, {None: 0, 'full': 1, 'x': 2}[spec['store']])
     spec = BWD_FORMS[form]
-    if spec['narrow']:                                       # launch_bwd (xw_ode_mfma4.h): narrow first, from the store only
+    if spec['narrow']:                                       # choose_sweep: narrow first, from the store only
         return ('bwd_n4', H, K, m, mid, spec['params'])
     store = FWD_FORMS[spec['producer']]['store'] is not None
-    if spec['adjoint'] or not store or mid > 1:              # xw_ode_bwd_recomp_w: k_ode_bwd<.., PARAMS, false, ADJ>
+    if spec['adjoint'] or not store or mid > 1:              # SWEEP_RECOMP, recomp_slot: k_ode_bwd<.., PARAMS, false, ADJ>
         return ('bwd', H, K, m, mid, spec['params'], False, spec['adjoint'])
     if spec['params']:
         return ('bwd_duo', H, K, m, mid)

@@ -26,7 +26,7 @@ Regions pinned as untouched (from the code):
   test-network MFMA containers    nothing: the record's padding columns ARE written (every lane of the ragged last tile stores a copy
                                   of the last valid point into a slot of its own, csrc/xw_disc_fwd.hip k_disc_fwd): all of it is checked
   fused containers                nothing: the activation store's padding columns ARE written (padding paths hold copies and have
-                                  slots of their own, csrc/xw_ode.hip act_store).  At (64, 16) every double row of the store is
+                                  slots of their own, csrc/xw_ode_core.h act_store).  At (64, 16) every double row of the store is
                                   checked as written; at (20, 10) the partial 4-row block (K mod 4 = 2) leaves slots unused inside the
                                   record, so the narrow-tile cases check its guards only
                                   (this file's cases.  tests/test_gpu_stepper_inventory.py pins more, from act_store: the 16-path
@@ -508,7 +508,7 @@ def test_wide_container_under_guards(N, L, d, m, solver):
         written = [job['u'], job['Y'], jx['gx'], jx['gs'], jp['gx'], jp['gs'], jp['gslab']]
         if with_act:
             # the store is [step][tile of 16 paths][rows][16]; K = 16 has no partial 4-row block, and the padding paths of the last
-            # tile store copies into slots of their own (csrc/xw_ode.hip act_store): every double row is written.  The last
+            # tile store copies into slots of their own (csrc/xw_ode_core.h act_store): every double row is written.  The last
             # 2 x words rows per stage hold the ReLU-mask words, which are not doubles (two words at depth 10): guard-checked only
             words = 2 if 4 * (m - 1) > 32 else 1
             stages = 1 if solver == 'euler' else 2

@@ -151,7 +151,7 @@ def test_merged_kind_is_the_sum_of_its_parts(family, H, K, m, solver):
 def test_merged_kind_refuses_incomplete_jobs(family, H, K, m):
     """kind 3 without the scalar pointer, the weight, v or the initial penalty's reference: XW_E_ARG from every family's entry point,
     before anything is launched; the complete job runs.  (Every stepper family forms kind 3: the fused containers in
-    csrc/xw_ode.hip, the generic path, the tiled family and both dopri5 steppers through csrc/xw_generic_cot.h -- there is no
+    csrc/xw_ode_core.h, the generic path, the tiled family and both dopri5 steppers through csrc/xw_generic_cot.h -- there is no
     family left to refuse the kind itself; an unknown kind, 4, is refused.)"""
     from xnode_wan_pde_solver_amd import kernels as KN
     from xnode_wan_pde_solver_amd._lib import XwOdeBwdJob, lib

@@ -15,7 +15,7 @@ own rounding spread (hidden units permuted, paths reversed; CPU), and a toleranc
 it -- it does not, the project's tolerances stand.  `python tests/test_gpu_stepper_inventory.py` prints the table (CPU only).
 
 Guards: every operand is a view of a guarded.Arena, outputs, slabs and stores start as the NaN pattern, and check() demands u, Y, gx,
-gs and the slabs written.  The activation store [step][tile of 16 paths][row][16], from csrc/xw_ode.hip (k_ode_fwd, act_store):
+gs and the slabs written.  The activation store [step][tile of 16 paths][row][16], from csrc/xw_ode_fwd.h and xw_ode_core.h (k_ode_fwd, act_store):
   full store (16-path forward)     every double row is written in all three containers.  K rows of a layer are whole 4-row blocks
                                    plus, at (20, 10), one partial block of K mod 4 = 2 rows whose 32 doubles the lane groups 0 and 1
                                    fill (ActLane.off_part_st; groups 2 and 3 carry an out-of-range offset); K mod 4 = 0 at (32, 12)
@@ -164,7 +164,7 @@ def _atoi(text):
 
 
 def test_duo_sweep_spacer_round():
-    """the duo sweep's spacer round (xw_ode_mfma4.h launch_bwd: jd.spread, tiles in (ncu, 2 ncu], i.e. above 4096 paths on this
+    """the duo sweep's spacer round (xw_ode_select.h duo_grid: spread, tiles in (ncu, 2 ncu], i.e. above 4096 paths on this
     chip): every second round of blocks ends at once and the tile index is folded back.  One tile more than the chip has CUs.  The
     branch is entered only under the launcher's own conditions -- XW_DUO_SPREAD not zero (read once per process, with atoi), its own
     count of CUs -- which the test mirrors but cannot observe; the result is compared with the oracle either way."""

@@ -22,6 +22,19 @@ def test_every_compiled_stepper_kernel_is_reached_and_every_form_lands_on_one():
     for k, users in want.items():
         forms = sorted(f for _, f in users)
         assert len({c for c, _ in users}) == 1 and forms in ([forms[0]], ['x_from_store', 'x_from_xstore']), (k, users)
+    # all instantiations of one kernel template at one width sit in one code object (what else a translation unit holds moves code
+    # generation); the recomputing k_ode_bwd (SAVED false: the width's _recomp object) count as a group of their own
+    objs = SI.code_objects(_lib.LIB_PATH)
+    group = lambda k: (k[0], k[1], k[2]) + ((k[6],) if k[0] == 'bwd' else ())      # noqa: E731
+    groups = {group(k) for k in have}
+    assert len(groups) == 2 * 6 + 4                  # fwd, fwd_n4, bwd from the store, recomputing bwd, bwd_duo, bwd_n4; no narrow tiles at (64, 16)
+    for g in sorted(groups, key=repr):
+        assert sum(1 for obj in objs if any(group(k) == g for k in obj)) == 1, g
+    # and what shares a code object, as csrc/xw_ode.hip says why: per width the forward kernels and the sweeps from the store in one,
+    # the recomputing sweeps in another
+    for obj in objs:
+        assert len({(k[1], k[2]) for k in obj}) == 1 and len({k[0] == 'bwd' and not k[6] for k in obj}) == 1, sorted(obj, key=repr)[:3]
+    assert len(objs) == 2 * len(SI.ODE_WIDTHS)
 
 
 def test_forms_per_case():

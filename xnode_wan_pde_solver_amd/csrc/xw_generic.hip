@@ -1,6 +1,6 @@
 // xw_generic.hip -- the GENERIC-WIDTH path of both networks: any u_hidden_dim <= 64, u_hidden_hidden_dim <= 16, v_hidden_dim <= 128.
 //
-// The reference accepts any widths (src/model.py:30-43, 62-85, 130-138).  The MFMA kernels of xw_ode.hip / xw_disc_*.hip are built
+// The reference accepts any widths (src/model.py:30-43, 62-85, 130-138).  The MFMA kernels of xw_ode_*.hip / xw_disc_*.hip are built
 // around the shipped shapes -- hidden-hidden activations are ONE 16-row tile, the test network's dVh maps four row tiles onto the
 // four waves of a block -- and serve (20,10), (32,12) and W = 50, 64 (narrower networks run exactly inside them, zero-padded).
 // Everything wider lands here: the same entry points (xw_ode_fwd_multi, xw_ode_bwd_multi, xw_disc_fwd, xw_disc_bwd: the dispatch

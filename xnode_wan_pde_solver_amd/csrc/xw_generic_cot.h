@@ -13,7 +13,7 @@ __device__ double cot_u(const XwOdeBwdJob& j, int l, int L, int path) {
   const long p = (long)l * j.N + path;
   if (j.res_u == nullptr) return j.ubar ? j.ubar[p] : 1.0;
   // merged: kind 1 with the A fields + (2 / I) kind 2.  Accepted here: res_scal[0] is loaded and 2 / I divided at EVERY
-  // (l, path) call, not once per wave in front of the time loop as the fused containers do (xw_ode.hip, make_cot) -- the
+  // (l, path) call, not once per wave in front of the time loop as the fused containers do (xw_ode_core.h, make_cot) -- the
   // families behind this header (generic, tiled, both dopri5 steppers) call cot_u from thirteen places in five kernels, none of
   // them on the headline path, and the same quotient of the same two doubles gives the same bits wherever it is formed.
   if (j.res_first_only == 3)

@@ -1,11 +1,11 @@
 // xw_ode_abi.hip -- public entry points of the stepper (include/xnwan.h): argument checks that do not depend on the
-// width, and the choice of the object compiled for (H, K) (xw_ode.hip, one object per width).
+// width, and the choice of the objects compiled for (H, K) (xw_ode_fwd.h, xw_ode.hip; the Makefile has the objects per width).
 #include "xw_common.h"
 #include "xnwan.h"
 #include "xw_generic.h"
 
 /* the containers (keep in step with the Makefile and kernels.ODE_WIDTHS): (20, 10) and (32, 12) on v_mfma_f64_4x4x4 (xw_ode_mfma4.h),
- * the WIDE container (64, 16) on v_mfma_f64_16x16x4 (round 6; xw_ode.hip -DXW_ODE_WIDE16, xw_ode_mfma16.h: one wave per tile, no
+ * the WIDE container (64, 16) on v_mfma_f64_16x16x4 (round 6; -DXW_ODE_WIDE16, xw_ode_mfma16.h: one wave per tile, no
  * narrow tiles); depths 1..10 and the same entry points in all of them */
 #define XW_ODE_WIDTHS(X) X(20, 10) X(32, 12) X(64, 16)
 
@@ -29,7 +29,7 @@ extern "C" int xw_ode_act_rows(int method, int H, int K, int m) {
   if (!width_compiled(H, K) || m < 1 || m > XW_ODE_MAX_LAYERS) return XW_E_DIMS;
   const int S = method == 0 ? 1 : method == 1 ? 2 : 0;           // rk4: the sweeps recompute
   // layer inputs + the stage inputs + the ReLU-mask words of every stage: (K + 3) / 4 bits per layer and lane, two rows per 32-bit
-  // word (XW_MASK_WORDS of xw_ode.hip: a second word only in the wide container at depth 10)
+  // word (XW_MASK_WORDS of xw_ode_core.h: a second word only in the wide container at depth 10)
   const int w = ((K + 3) / 4) * (m - 1) > 32 ? 4 : 2;
   return S == 0 ? 0 : S * m * K + (S - 1) * H + w * S;
 }

@@ -1,8 +1,12 @@
 // xw_ode_mfma16.h -- the stepper's field on v_mfma_f64_16x16x4: the form of the WIDE container (64, 16), selected by -DXW_ODE_WIDE16
 // (round 6).  Whole 16-row tiles, bias gradients as row sums -- no ones row, no 4x4 blocks, no narrow tiles; a duo sweep of its own.
-// Included by xw_ode.hip inside its anonymous namespace, three times: XW_ODE_SECTION 1 = the field (operands, evaluation, vector-
-// Jacobian product, gradient accumulators, the duo sweep's LDS plan), 2 = storing the gradients and the duo sweep's second wave, 3 = the launchers.
-#if XW_ODE_SECTION == 1      // ---- the field
+// Included once: the field (operands, evaluation, vector-Jacobian product, gradient accumulators, the duo sweep's LDS plan), then
+// storing the gradients and the duo sweep's second wave.
+#pragma once
+#include "xw_ode_core.h"
+
+namespace {
+
 static_assert(XW_ODE_K == 16 && XW_ODE_H % 16 == 0 && XW_ODE_H <= 64, "the wide container: K = 16, H a multiple of 16 up to 64");
 // K = 16 and H = 16 HT are whole 16-row tiles, so the 16x16x4 form wastes nothing (at K = 10 it ran 10 of 16 rows): a [K x K]
 // layer is 4 chained instructions, Win's y-part H / 4, Wo HT x 4.  An A-fragment is ONE double per lane and (tile, k-step):
@@ -160,7 +164,8 @@ __device__ __forceinline__ void field_vjp(const FieldW<H, K>& w, const FieldWT<H
     for (int ks = 0; ks < D::KSK; ++ks) yb[ht] = XW_MFMA(wT.WyT[ht][ks], zb[ks], yb[ht]);
   }
 }
-#elif XW_ODE_SECTION == 2    // ---- the field gradients: into the slab; the duo sweep's second wave
+
+// ---- the field gradients: into the slab; the duo sweep's second wave
 // the field's weight-gradient accumulators -> one slab (wide container: the biases and the time column are row sums over the 16 paths)
 template <int H, int K, bool HID = true, bool IO = true>
 __device__ __forceinline__ void store_field_grads(double* slab, const UOff& o, int d, const FieldG<H, K>& G) {
@@ -321,30 +326,5 @@ __device__ __forceinline__ void duo_outer(const BwdJobs& jobs, const double* __r
       if (16 * ht + j < H) slab[o.Wob + 16 * ht + j] = sbo[ht];
   }
 }
-#elif XW_ODE_SECTION == 3    // ---- launchers
-// (no narrow tiles: a launch that asks for them runs the 16-path kernels)
-template <int H, int K, int M>
-bool launch_fwd_narrow(int, const FwdJobs&, const double*, const double*, int, int, dim3, hipStream_t, int&) { return false; }
-template <int H, int K, int M, bool PARAMS>
-int launch_bwd(int method, const BwdJobs& jobs, const double* t, const double* theta, int L, int d, bool adj, bool narrow,
-               hipStream_t s) {
-  const dim3 grid(jobs.tile0[jobs.n]), block(64);
-  // the wide container: no narrow tiles; the recomputing sweeps form their weight gradients themselves (OUTER = 1)
-  bool act_ = true;
-  for (int i = 0; i < jobs.n; ++i) act_ = act_ && jobs.act[i] != nullptr;
-  if (adj || !act_ || method > 1)
-    return XW_ODE_FN(xw_ode_bwd_recomp_w)(&jobs, t, theta, method, L, d, M, PARAMS ? 1 : 0, adj ? 1 : 0, (void*)s);
-  // from the activation store: without weight gradients one wave per tile, with them the duo sweep (chain wave + partner wave)
-  if (PARAMS) {
-    BwdJobs jd = jobs;
-    jd.spread = 0;
-    if (method == 0) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 0>), grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-    else hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 1>), grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-  } else {
-    if (method == 0) hipLaunchKernelGGL((k_ode_bwd<H, K, M, 0, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-    else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 1, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-  }
-  return xw_launch_status();
-}
-#endif
-#undef XW_ODE_SECTION
+
+}  // namespace

@@ -1,8 +1,11 @@
 // xw_ode_mfma4.h -- the stepper's field on v_mfma_f64_4x4x4: the form of the narrow containers (20, 10) and (32, 12), i.e. of
-// every build of xw_ode.hip WITHOUT -DXW_ODE_WIDE16.  Included by xw_ode.hip inside its anonymous namespace, three times:
-// XW_ODE_SECTION 1 = the field (operands, evaluation, vector-Jacobian product, gradient accumulators, the duo sweep's LDS plan),
-// 2 = storing the gradients and the duo sweep's second wave, 3 = the narrow tiles (xw_ode_n4.h) and the launchers.
-#if XW_ODE_SECTION == 1      // ---- the field
+// every build of xw_ode_fwd.h / xw_ode.hip WITHOUT -DXW_ODE_WIDE16.  Included once: the field (operands, evaluation, vector-
+// Jacobian product, gradient accumulators, the duo sweep's LDS plan), then storing the gradients and the duo sweep's second wave.
+#pragma once
+#include "xw_ode_core.h"
+
+namespace {
+
 static_assert(XW_ODE_K <= 15, "row K of the 16-row K-tile is the ones row that collects the bias gradients");
 static_assert(Dim<XW_ODE_H, XW_ODE_K>::HT <= 2 && Dim<XW_ODE_H, XW_ODE_K>::CT <= 3, "H <= 32");
 // The field's layers run on v_mfma_f64_4x4x4_4b_f64: one instruction = a 4x4 weight block times 4 rows x 16 paths of
@@ -118,6 +121,13 @@ template <int H, int K, int M> struct DuoPlan {
   static constexpr int BUF = XW_TSTRIDE * (16 * (HT - 1) + HLAST + KROWS * M + 16);   // (+ 16 rows: reads past the last tile)
   static_assert(BUF >= 3 * XW_TTILE, "the chain wave's epilogue borrows a buffer for its three transpose tiles");
 };
+// vector-Jacobian product of one field evaluation.  ob: cotangent of F's output; returns the cotangent of the y input
+// in yb, adds the cotangent of z0 into xpb (= cotangent of the x-projection and of Win.b), and (PARAMS) accumulates the
+// parameter gradients (outer products over the 16 paths; in the 4x4x4 form a row of ones / the time row in the R tile makes the bias and
+// time-column gradients ride along as an extra accumulator column).
+// OUTER: 0 = no weight gradients, 1 = this wave forms them itself (outer products through its own LDS tiles),
+//        2 = "duo" sweep: this wave only posts the cotangent tiles (transposed) into `lds` = the evaluation's Q buffer
+//            (DuoPlan), a partner wave of the block contracts them with the activations it loads itself.
 template <int H, int K, int M, int OUTER, class SV>
 __device__ __forceinline__ void field_vjp(const FieldW<H, K>& w, const FieldWT<H, K>& wT, double t, const SV& sv,
                                           const d4 (&yin)[Dim<H, K>::HT], const d4 (&ob)[Dim<H, K>::HT],
@@ -210,7 +220,8 @@ __device__ __forceinline__ void field_vjp(const FieldW<H, K>& w, const FieldWT<H
     __builtin_amdgcn_wave_barrier();
   }
 }
-#elif XW_ODE_SECTION == 2    // ---- the field gradients: into the slab; the duo sweep's second wave
+
+// ---- the field gradients: into the slab; the duo sweep's second wave
 // the field's weight-gradient accumulators -> one slab
 template <int H, int K, bool HID = true, bool IO = true>
 __device__ __forceinline__ void store_field_grads(double* slab, const UOff& o, int d, const FieldG<H, K>& G) {
@@ -447,67 +458,5 @@ __device__ __forceinline__ void duo_outer(const BwdJobs& jobs, const double* __r
       }
     }
 }
-#elif XW_ODE_SECTION == 3    // ---- launchers
-#include "xw_ode_n4.h"
 
-// narrow tiles (xw_ode_n4.h): the same grid of 16-path tiles, four waves of 4 paths each.  sel: method * 3 + store mode, as in
-// launch_fwd; false: the launch does not ask for them
-template <int H, int K, int M>
-bool launch_fwd_narrow(int sel, const FwdJobs& jobs, const double* t, const double* theta, int L, int d, dim3 grid, hipStream_t s, int& rc) {
-  if (!jobs.narrow) return false;
-  rc = XW_E_ARG;
-  switch (sel) {
-    case 0: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 1: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 1>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 2: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 0, 2>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 3: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 4: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 1>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 5: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 1, 2>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    case 6: hipLaunchKernelGGL((n4::k_ode_fwd_n4<H, K, M, 2, 0>), grid, dim3(256), 0, s, jobs, t, theta, L, d); break;
-    default: return true;
-  }
-  rc = xw_launch_status();
-  return true;
-}
-template <int H, int K, int M, bool PARAMS>
-int launch_bwd(int method, const BwdJobs& jobs, const double* t, const double* theta, int L, int d, bool adj, bool narrow,
-               hipStream_t s) {
-  const dim3 grid(jobs.tile0[jobs.n]), block(64);
-  if (narrow) {
-    // narrow tiles (xw_ode_n4.h): the same grid of 16-path tiles, four waves of 4 paths each; from the activation store only
-    if (adj || method > 1) return XW_E_ARG;
-    for (int i = 0; i < jobs.n; ++i)
-      if (jobs.act[i] == nullptr) return XW_E_ARG;
-    if (method == 0) hipLaunchKernelGGL((n4::k_ode_bwd_n4<H, K, M, 0, PARAMS>), grid, dim3(256), 0, s, jobs, t, theta, L, d);
-    else hipLaunchKernelGGL((n4::k_ode_bwd_n4<H, K, M, 1, PARAMS>), grid, dim3(256), 0, s, jobs, t, theta, L, d);
-    return xw_launch_status();
-  }
-  bool act = true;                                     // all jobs or none (checked by the caller)
-  for (int i = 0; i < jobs.n; ++i) act = act && jobs.act[i] != nullptr;
-  if (adj || !act || method > 1)      // (the recomputing sweeps live in an object of their own: xw_ode.hip, XW_ODE_PART_RECOMP)
-    return XW_ODE_FN(xw_ode_bwd_recomp_w)(&jobs, t, theta, method, L, d, M, PARAMS ? 1 : 0, adj ? 1 : 0, (void*)s);
-  // two rounds of tiles over the CUs: a spacer round in between (k_ode_bwd_duo)
-  static const int spread_on = [] { const char* e = getenv("XW_DUO_SPREAD"); return e ? atoi(e) : 1; }();
-  static const int ncu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; return n; }();
-  const int tiles = jobs.tile0[jobs.n];
-  BwdJobs jd = jobs;
-  // (exactly two rounds: 103 against 142 us at 512 tiles; with three rounds the third block of a CU meets the first again either
-  //  way -- 149 against 145 us --, and from four rounds on every SIMD hosts two waves whatever the order)
-  jd.spread = (spread_on && ncu > 0 && tiles > ncu && tiles <= 2 * ncu) ? ncu : 0;
-  const int rounds = jd.spread ? (tiles + ncu - 1) / ncu : 0;
-  const dim3 duo_grid(jd.spread ? (2 * (rounds - 1)) * ncu + (tiles - (rounds - 1) * ncu) : tiles);
-  switch (method) {
-    case 0:
-      if (PARAMS) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 0>), duo_grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 0, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-      break;
-    case 1:
-      if (PARAMS) hipLaunchKernelGGL((k_ode_bwd_duo<H, K, M, 1>), duo_grid, dim3(XW_DUO_THREADS), 0, s, jd, t, theta, L, d);
-      else hipLaunchKernelGGL((k_ode_bwd<H, K, M, 1, false, true>), grid, block, 0, s, jobs, t, theta, L, d);
-      break;
-    default: return XW_E_ARG;
-  }
-  return xw_launch_status();
-}
-#endif
-#undef XW_ODE_SECTION
+}  // namespace

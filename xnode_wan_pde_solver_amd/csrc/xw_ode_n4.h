@@ -1,5 +1,5 @@
-// xw_ode_n4.h -- NARROW-TILE stepper kernels: one wave = 4 Monte-Carlo paths x 16 rows (included by xw_ode_mfma4.h, inside xw_ode.hip's
-// anonymous namespace; same jobs, same activation store, same slabs, same results as the 16-path kernels).
+// xw_ode_n4.h -- NARROW-TILE stepper kernels: one wave = 4 Monte-Carlo paths x 16 rows (included by xw_ode_fwd.h and
+// xw_ode.hip in the 4x4x4 form; same jobs, same activation store, same slabs, same results as the 16-path kernels).
 //
 // Why.  A 16-path tile is ONE instruction stream; N = 4096 paths are 256 of them for the chip's 1024 SIMDs, and a stream is
 // a dependent chain (62 field evaluations x 9 layers per sweep): alone on the chip the 16-path sweeps run at 0.1 - 0.2 of
@@ -33,7 +33,10 @@
 // H > 16: the hidden state is two registers.  For 16 < H <= 20 the second one holds rows 16..19 REPLICATED in all four
 // blocks: as an input it then needs one instruction instead of four, as an output the four rotations leave the complete sum
 // in every block for free.  Wider (H <= 32): rows 16..31 as a second natural register.
+#pragma once
+#include "xw_ode_core.h"
 
+namespace {
 namespace n4 {
 
 template <int C> __device__ __forceinline__ int rot_i(int x) {
@@ -668,7 +671,7 @@ __global__ void __launch_bounds__(256, 2) k_ode_fwd_n4(const FwdJobs jobs, const
     }
   }
   // lane offsets (bytes) into the activation store's tile (C layout).  Every store of the time loop goes through a buffer
-  // descriptor and lanes that own nothing carry an out-of-range offset (ActLane.off_part_st in xw_ode.hip: a branch on a lane
+  // descriptor and lanes that own nothing carry an out-of-range offset (ActLane.off_part_st in xw_ode_core.h: a branch on a lane
   // predicate around one store per layer cost more than the layer's four matrix instructions)
   const unsigned cK = 4 * g.b + g.hi < K ? 8u * (unsigned)koff<K>(g.b, g.hi, 4 * g.q + g.lo) : XW_ACT_OOB;
   unsigned cY[D::NY], oY[D::NY];
@@ -707,7 +710,7 @@ __global__ void __launch_bounds__(256, 2) k_ode_fwd_n4(const FwdJobs jobs, const
     unsigned bits = 0;
 #pragma unroll
     for (int j = 0; j < M - 1; ++j) {
-      // (the bit is z > 0, not the sign: a dead layer feeds exact +0 to the next one and relu'(+0) = 0, xw_ode.hip SaveX)
+      // (the bit is z > 0, not the sign: a dead layer feeds exact +0 to the next one and relu'(+0) = 0, xw_ode_core.h SaveX)
       bits = (bits << D::KB) | (z > 0.0 ? 1u : 0u);
       const double r = xw_relu1(z);
       if (ACT == 1) st64(r, rs, cK, (i * AL::STAGE + j * K) * 16 * 8, 2);      // (nt: streamed, read once, by a sweep)
@@ -781,3 +784,4 @@ __global__ void __launch_bounds__(256, 2) k_ode_fwd_n4(const FwdJobs jobs, const
 
 #undef st64
 }  // namespace n4
+}  // namespace

@@ -1,7 +1,7 @@
 // xw_tiled.hip -- the TILED stepper family: u_theta's forward pass and its reverse sweep at the network's own runtime widths,
 // u_hidden_dim H <= 256, u_hidden_hidden_dim K <= 256, u_layers 1..32, fixed-grid euler / midpoint / rk4 (3/8 rule).
 //
-// The fused kernels of xw_ode.hip keep a path tile's state and the field's weights in registers, sized at compile time, and stop
+// The fused kernels of xw_ode_fwd.h / xw_ode.hip keep a path tile's state and the field's weights in registers, sized at compile time, and stop
 // at (64, 16); the generic path (xw_generic.hip) runs one path per lane on the vector ALU and stops at the same widths.  Here
 // one wave owns a tile of 16 paths for every step of a job and runs every layer of the field as a [K_out x K_in] . [K_in x 16]
 // product on v_mfma_f64_16x16x4 (xw_common.h: "chain layout", features on the rows, the 16 paths on the columns), the widths

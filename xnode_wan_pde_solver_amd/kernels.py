@@ -68,7 +68,7 @@ def method_id(name):
     return METHODS[name]
 
 
-# Kernel instantiations (csrc/xw_ode.hip XW_ODE_DISPATCH, csrc/xw_disc_fwd.hip, xw_disc_rec.hip, xw_disc_bwd.hip): widths the MFMA kernels are compiled for.  Any
+# Kernel instantiations (the tables of csrc/xw_ode_fwd.h and xw_ode.hip, csrc/xw_disc_fwd.hip, xw_disc_rec.hip, xw_disc_bwd.hip): widths the MFMA kernels are compiled for.  Any
 # smaller network runs EXACTLY inside the next larger instantiation: its parameters are embedded in a zero-padded blob
 # (nets.Blob) -- padding units have zero in- and outgoing weights and zero bias, so they stay identically zero through
 # relu / tanh, contribute exact zeros to every sum, and receive exactly zero gradients (Adam leaves them at zero).
