@@ -27,7 +27,6 @@ gs and the slabs written.  The activation store [step][tile of 16 paths][row][16
                                    forward (csrc/xw_ode_n4.h) has store code of its own: guard bands only
 """
 import os
-import re
 import sys
 
 import pytest
@@ -93,13 +92,22 @@ def _store_regions(act, tiles, H, K, m, stages, x_only):
     return [(rec, full(row < doubles))], []
 
 
-def _run(c, n, l, d, seed, forms):
-    """every form of `forms` at case c on n paths, l times: launches in one arena, guards, then the comparisons"""
+def _run(c, n, l, d, seed, forms, switch_sets=({},)):
+    """every form of `forms` at case c on n paths, l times: launches in one arena, guards, then the comparisons -- once per entry of
+    `switch_sets` (library switches, the arguments of kernels.switched), every time against the same oracle"""
     from xnode_wan_pde_solver_amd import kernels as KN
+    oracle = _fused_oracle(c[0], c[1], c[2], d, n, l, c[3], seed)
+    adjoint = []                                    # (the adjoint oracle's gradients, once a form asks for them)
+    for sw in switch_sets:
+        with KN.switched(**sw):
+            _run_once(KN, c, n, l, d, forms, oracle, adjoint)
+
+
+def _run_once(KN, c, n, l, d, forms, oracle, adjoint):
     H, K, m, method = c
     assert KN.stepper_family(H, K, m) == 'mfma'
     tol_v, tol_g, tol_a = _tolerances(c)
-    theta, blob, x, t, start, ubar, u_ref, Y_ref, leaves = _fused_oracle(H, K, m, d, n, l, method, seed)
+    theta, blob, x, t, start, ubar, u_ref, Y_ref, leaves = oracle
     mid = KN.method_id(method)
     rows, cols, P = KN.ode_act_rows(mid, H, K, m), KN.ode_act_cols(n), blob.numel()
     stages = {'euler': 1, 'midpoint': 2, 'rk4': 4}[method]
@@ -135,15 +143,14 @@ def _run(c, n, l, d, seed, forms):
         _close(job['u'].t(), u_ref.detach(), tol_v, f + ' u')
         _close(job['Y'], Y_ref, tol_v, f + ' Y')
     want = _grads(u_ref, leaves, ubar)
-    want_adj = None
     for f, j in sweeps.items():
         if SI.BWD_FORMS[f]['adjoint']:
-            if want_adj is None:
+            if not adjoint:
                 u_adj, leaves_adj = _adjoint_oracle(theta, m, method, x, t, start)
-                want_adj = _grads(u_adj, leaves_adj, ubar)
-                assert float(want_adj[0].abs().max()) == 0.0        # x is not an input of odeint_adjoint
+                adjoint.append(_grads(u_adj, leaves_adj, ubar))
+                assert float(adjoint[0][0].abs().max()) == 0.0      # x is not an input of odeint_adjoint
             assert float(j['gx'].abs().max()) == 0.0, f + ' gx'
-            w, tol = want_adj, tol_a
+            w, tol = adjoint[0], tol_a
         else:
             _close(j['gx'].t(), want[0], tol_g, f + ' gx')
             w, tol = want, tol_g
@@ -157,22 +164,17 @@ def test_every_form_against_the_oracle(c):
     _run(c, N, L, D, SEED0 + 10 * SI.CASES.index(c), SI.forms_of(*c))
 
 
-def _atoi(text):
-    """C's atoi: optional blanks and sign, then the leading digits; 0 if there are none"""
-    m = re.match(r'\s*([+-]?\d+)', text)
-    return int(m.group(1)) if m else 0
-
-
 def test_duo_sweep_spacer_round():
     """the duo sweep's spacer round (xw_ode_select.h duo_grid: spread, tiles in (ncu, 2 ncu], i.e. above 4096 paths on this
-    chip): every second round of blocks ends at once and the tile index is folded back.  One tile more than the chip has CUs.  The
-    branch is entered only under the launcher's own conditions -- XW_DUO_SPREAD not zero (read once per process, with atoi), its own
-    count of CUs -- which the test mirrors but cannot observe; the result is compared with the oracle either way."""
+    chip): every second round of blocks ends at once and the tile index is folded back.  One tile more than the chip has CUs, with
+    the library switch duo_spread on (the default, read back from the library) and once more with it off: one block per tile.  The
+    launcher's own count of CUs the test mirrors but cannot observe; the result is compared with the oracle either way."""
+    from xnode_wan_pde_solver_amd import kernels as KN
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    assert _atoi(os.environ.get('XW_DUO_SPREAD', '1')) != 0          # (the launcher's switch, parsed as it parses it)
+    assert KN.switches()['duo_spread'] is True
     n = 16 * (ncu + 1)
     assert ncu < (n + 15) // 16 <= 2 * ncu
-    _run((20, 10, 8, 'midpoint'), n, 2, D, SEED0 - 1, ['fwd_store', 'duo'])
+    _run((20, 10, 8, 'midpoint'), n, 2, D, SEED0 - 1, ['fwd_store', 'duo'], switch_sets=({}, dict(duo_spread=False)))
 
 
 # ---- the oracle's own rounding spread (CPU) ------------------------------------------------------------------------------------------

@@ -27,12 +27,11 @@ the oracle with the hidden units permuted and the points reversed, CPU -- and a 
 eighth of it; it does not: the project's tolerances stand.  `python tests/test_gpu_testnet_inventory.py --spread` prints the table
 (CPU only).
 
-The kernels behind XW_DISC_VIN_LDS=0 (k_disc_fwd<50 | 64, *, *, 0>) and the rotated first round of the static split behind
-XW_DISC_DYNAMIC=0 need a process of their own (the switches are read once per process): one child per variable runs this module's
-__main__ on the named cases -- the same case function -- and prints `ok <case id>` per case.
+The kernels behind disc_vin_lds off (k_disc_fwd<50 | 64, *, *, 0>) and the rotated first round of the static split behind
+disc_dynamic off run in this process like every other case: run_case issues a case's launches inside kernels.switched(...) with the
+library switches the case is described with (options.EngineOptions; the library reads them at each launch call).
 """
 import os
-import subprocess
 import sys
 
 import pytest
@@ -49,11 +48,6 @@ from test_gpu_tiled_stepper import _close  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 SEED0 = 4000                                        # case i of TI.CASES is seeded 4000 + 10 i
-# seconds per child.  NOT yet measured on the device (profiles/r17_testnet_inventory.md says so): reasoned from the sibling inventory
-# file, whose first case takes 1.4 s (it loads the library's code objects) and every later one a few hundredths of a second on the
-# GPU side -- a child is an interpreter start, the imports, that first load and 8 (4) such cases.  To be replaced by a few times the
-# measured in-process time of 8 cases once the file has run on an MI355X.
-CHILD_TIMEOUT = 120
 
 
 def _seed(c):
@@ -120,8 +114,9 @@ def operands(arena, c, ref):
 def launches(c, ops):
     """the case's calls of kernels.disc_xproj / disc_fwd / disc_bwd / disc_gradx"""
     from xnode_wan_pde_solver_amd import kernels as KN
-    for var in TI.SWITCHES.values():                # the process runs under the switches the case is described with
-        assert ('0' if os.environ.get(var, '')[:1] == '0' else '1') == TI.switches(c).get(var, '1'), (var, os.environ.get(var))
+    now = KN.switches()                             # the library stands at the switches the case is described with
+    for attr, field in TI.SWITCHES.items():
+        assert now[field] == getattr(c, attr), (TI.ENV[field], now[field])
     if c.entry == 'gradx':
         KN.disc_gradx(ops['xT'], ops['t'], ops['phi'], c.W, c.q, tpp=ops['tpp'], vbar=ops['vbar'], gxv=ops['gxv'], gtv=ops['gtv'],
                       family=c.family)
@@ -202,38 +197,22 @@ def run_case(c, device=DEVICE):
     ref = reference(c)
     arena = G.Arena(torch.device(device))
     ops = operands(arena, c, ref)
-    launches(c, ops)
+    with KN.switched(**TI.switched_off(c)):         # (read on the host when a launch is called: the block need not outlast the kernels)
+        launches(c, ops)
     verify(arena, c, ops, ref)
 
 
-IN_PROCESS = [c for c in TI.CASES if TI.in_process(c)]
-CHILDREN = {var: [c for c in TI.CASES if TI.switches(c) == {var: '0'}] for var in ('XW_DISC_VIN_LDS', 'XW_DISC_DYNAMIC')}
-assert len(IN_PROCESS) + sum(len(v) for v in CHILDREN.values()) == len(TI.CASES)
+# 111 cases at the defaults, 8 behind disc_vin_lds off, 4 behind disc_dynamic off
+BEHIND = {field: [c for c in TI.CASES if TI.switched_off(c) == {field: False}] for field in ('disc_vin_lds', 'disc_dynamic')}
+assert sum(TI.in_process(c) for c in TI.CASES) == 111 and {f: len(v) for f, v in BEHIND.items()} == {'disc_vin_lds': 8, 'disc_dynamic': 4}
+assert 111 + 8 + 4 == len(TI.CASES)
 assert {TI.cid(c) for c in TI.CASES if _corner(c)} == set(ORACLE_SPREAD)
 
 
-@pytest.mark.parametrize('c', IN_PROCESS, ids=TI.cid)
+@pytest.mark.parametrize('c', TI.CASES, ids=TI.cid)
 def test_case_against_the_oracle_under_guards(c):
     assert not _corner(c) or TI.cid(c) in ORACLE_SPREAD
     run_case(c)
-
-
-@pytest.mark.parametrize('var', sorted(CHILDREN))
-def test_cases_behind_a_process_wide_switch(var):
-    """a fresh child process with that one variable set to 0 runs the cases; nothing is retried"""
-    cases = CHILDREN[var]
-    assert cases and os.environ.get(var) is None
-    env = dict(os.environ)
-    env[var] = '0'
-    cmd = [sys.executable, os.path.abspath(__file__)] + [TI.cid(c) for c in cases]
-    try:
-        r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout.decode(errors='replace') if isinstance(e.stdout, bytes) else (e.stdout or '')
-        pytest.fail('%s=0: the child ran into its limit of %d s\n%s' % (var, CHILD_TIMEOUT, out))
-    print(r.stdout)
-    assert r.returncode == 0, '%s=0: the child ended with %d\n%s' % (var, r.returncode, r.stdout)
-    assert [ln for ln in r.stdout.splitlines() if ln.startswith('ok ')] == ['ok ' + TI.cid(c) for c in cases], r.stdout
 
 
 def test_depth_17_with_the_fused_gradient_is_refused():
@@ -284,14 +263,8 @@ def oracle_spread(c):
     return rel(flip(v2.detach()), v), max(rel(gX2[..., 0], gX[..., 0]), rel(gX2[..., 1:], gX[..., 1:])), sg
 
 
-if __name__ == '__main__':
-    if '--spread' in sys.argv:
-        print('| case | v | vt, gxv, gtv | phi gradient | tolerances |')
-        for c_ in TI.CASES:
-            if _corner(c_) or '--all' in sys.argv:
-                print('| %s | %.2e | %.2e | %.2e | %s |' % ((TI.cid(c_),) + oracle_spread(c_) + (_tolerances(c_),)))
-        sys.exit(0)
-    by_id = {TI.cid(c_): c_ for c_ in TI.CASES}
-    for name in sys.argv[1:]:
-        run_case(by_id[name])
-        print('ok ' + name, flush=True)
+if __name__ == '__main__' and '--spread' in sys.argv:
+    print('| case | v | vt, gxv, gtv | phi gradient | tolerances |')
+    for c_ in TI.CASES:
+        if _corner(c_) or '--all' in sys.argv:
+            print('| %s | %.2e | %.2e | %.2e | %s |' % ((TI.cid(c_),) + oracle_spread(c_) + (_tolerances(c_),)))

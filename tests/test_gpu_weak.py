@@ -24,16 +24,14 @@ factor of 10 left; one dropped term of 270,435 is 4e-6 x sum_abs.  Loss values s
 compared per time row group (l = 0, where the alpha-weighted initial penalty sets the scale, apart from l > 0).
 
 Launch shapes (csrc/xw_weak.hip reduce_cap / reduce_threads): 1024 threads; 128 blocks up to 2^18 points, 256 above.  (4099, 33, 4)
-is 135,267 points: a second grid-stride trip; (8195, 33, 4) is 270,435: the 256-block cap.  XW_REDUCE_THREADS=256 with
-XW_REDUCE_BLOCKS=3 (four waves per block, three blocks, many trips) is read once per process: one fresh child runs this module's
-__main__ on the small shapes' case ids -- the same case function -- and prints `ok <case id>` per case.
+is 135,267 points: a second grid-stride trip; (8195, 33, 4) is 270,435: the 256-block cap.  The library switches reduce_threads=256
+with reduce_blocks=3 (four waves per block, three blocks, many trips): the small shapes' cases once more, through the same case
+function, inside kernels.switched(...).
 
-`python tests/test_gpu_weak.py` (no arguments, CPU only) prints the case tables and the reference-vs-exact gaps.
+`python tests/test_gpu_weak.py` (CPU only) prints the case tables and the reference-vs-exact gaps.
 """
 import os
-import subprocess
 import sys
-import time
 
 import pytest
 import torch
@@ -49,11 +47,6 @@ pytestmark = pytest.mark.gpu
 F64 = torch.float64
 DEVICE = 'cuda'
 ORACLE_SPREAD = W.ORACLE_SPREAD
-# The child's limit: 10 x the measured time of the child as a whole -- an interpreter start with the imports, the first load of the
-# library's code objects and the small cases with their references.  Measured on an MI355X: the test took 2.53 s (the same cases
-# take 0.6 s in process: one first case of 0.4 s and 0.01 s each after it); profiles/r18_weak_kernels.md.
-CHILD_MEASURED = 2.6
-CHILD_TIMEOUT = 10 * CHILD_MEASURED
 
 
 def _counter(arena, value, name):
@@ -257,20 +250,13 @@ def test_workspace_contract():
 
 
 # ---- the process-wide launch-shape switches --------------------------------------------------------------------------------------------------
-def test_small_shapes_with_three_blocks_of_four_waves():
-    """XW_REDUCE_THREADS=256, XW_REDUCE_BLOCKS=3 in one fresh child process: the small shapes' cases; nothing is retried"""
-    assert os.environ.get('XW_REDUCE_THREADS') is None and os.environ.get('XW_REDUCE_BLOCKS') is None
-    env = dict(os.environ, XW_REDUCE_THREADS='256', XW_REDUCE_BLOCKS='3')
-    ids = [W.wid(c) for c in W.SMALL_CASES]
-    cmd = [sys.executable, os.path.abspath(__file__)] + ids
-    try:
-        res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout.decode(errors='replace') if isinstance(e.stdout, bytes) else (e.stdout or '')
-        pytest.fail('the child ran into its limit of %d s\n%s' % (CHILD_TIMEOUT, out))
-    print(res.stdout[-4000:])
-    assert res.returncode == 0, 'the child ended with %d\n%s' % (res.returncode, res.stdout[-8000:])
-    assert [ln for ln in res.stdout.splitlines() if ln.startswith('ok ')] == ['ok ' + i for i in ids], res.stdout[-8000:]
+@pytest.mark.parametrize('c', W.SMALL_CASES, ids=W.wid)
+def test_small_shapes_with_three_blocks_of_four_waves(c):
+    """the small shapes' cases under the library switches reduce_threads=256, reduce_blocks=3"""
+    from xnode_wan_pde_solver_amd import kernels as KN
+    with KN.switched(reduce_threads=256, reduce_blocks=3):
+        assert (KN.switches()['reduce_threads'], KN.switches()['reduce_blocks']) == (256, 3)
+        run_case(c)
 
 
 # ---- Adam --------------------------------------------------------------------------------------------------------------------------------------
@@ -310,13 +296,6 @@ def test_adam_against_the_oracle(c):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) > 1:
-        for name in sys.argv[1:]:
-            t0 = time.time()
-            run_case(W.BY_ID[name])
-            print('ok ' + name, flush=True)
-            print('   (%.2f s)' % (time.time() - t0), flush=True)
-        sys.exit(0)
     print('| weak-form case | points | launches | I: abs(oracle - exact) / sum_abs | abs(I) / sum_abs | worst gap of the other sums |')
     for c_ in W.WEAK_CASES:
         r_ = W.reference(c_)

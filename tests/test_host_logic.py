@@ -586,6 +586,96 @@ def test_engine_options_are_read_from_the_environment_once_and_in_one_place(monk
     monkeypatch.setenv('XW_REPLICATE_BELOW', '0')
     o = EngineOptions.from_env()
     assert o.non_default() == {'use_graphs': False, 'xproj_min_d': 7, 'pairwise_single_slice': False, 'prio_drop_A': 2, 'replicate_below': 0}
+    # the library switches: '0' turns a flag off, the numbers as the launch shapes can take them (anything else: the default)
+    for var in ('XW_GRAPHS', 'XW_XPROJ_MIN_D', 'XW_ELEMENTWISE_SINGLE_SLICE', 'XW_PRIO_DROP_A', 'XW_REPLICATE_BELOW'):
+        monkeypatch.delenv(var)
+    off = {'XW_DISC_DYNAMIC': 'disc_dynamic', 'XW_DISC_VIN_LDS': 'disc_vin_lds', 'XW_DISC_REC_TSUM': 'disc_rec_tsum',
+           'XW_DUO_SPREAD': 'duo_spread', 'XW_LONE_NARROW': 'lone_narrow'}
+    for var, field in off.items():
+        monkeypatch.setenv(var, '1')
+        assert EngineOptions.from_env().non_default() == {}
+        monkeypatch.setenv(var, '0')
+        assert EngineOptions.from_env().non_default() == {field: False}
+        monkeypatch.delenv(var)
+    for var, field, cases in (('XW_REDUCE_BLOCKS', 'reduce_blocks', {'3': 3, '1024': 1024, '0': 0, '1025': 0, '-1': 0}),
+                              ('XW_REDUCE_THREADS', 'reduce_threads', {'256': 256, '512': 512, '1024': 1024, '128': 1024, '0': 1024})):
+        for text, want in cases.items():
+            monkeypatch.setenv(var, text)
+            assert getattr(EngineOptions.from_env(), field) == want, (var, text)
+        monkeypatch.delenv(var)
+    for var in list(off) + ['XW_REDUCE_BLOCKS', 'XW_REDUCE_THREADS']:
+        monkeypatch.setenv(var, {'XW_REDUCE_BLOCKS': '3', 'XW_REDUCE_THREADS': '256'}.get(var, '0'))
+    assert EngineOptions.from_env().non_default() == dict({f: False for f in off.values()}, reduce_blocks=3, reduce_threads=256)
     pkg = os.path.join(ROOT, 'xnode_wan_pde_solver_amd')
-    for name in ('engine.py', 'solver.py'):
+    for name in ('engine.py', 'solver.py', 'kernels.py'):
         assert 'os.environ' not in open(os.path.join(pkg, name)).read(), name
+    # ... and the C library reads none: its switches are set through include/xnwan_switches.h
+    csrc = os.path.join(pkg, 'csrc')
+    for name in sorted(os.listdir(csrc)):
+        if os.path.isfile(os.path.join(csrc, name)) and not name.endswith(('.o', '.d')):
+            assert 'getenv' not in open(os.path.join(csrc, name), errors='replace').read(), name
+
+
+def test_library_switches_round_trip_and_refuse_bad_values():
+    """include/xnwan_switches.h on the host (no device): the library starts at EngineOptions' defaults, kernels' import applies
+    from_env(), set / get round-trip every field, every refused input leaves the value alone, switched() restores on an exception,
+    and the header's names are SWITCH_SIGNATURES and exported"""
+    import ctypes
+    import dataclasses
+    from xnode_wan_pde_solver_amd import kernels as KN
+    from xnode_wan_pde_solver_amd.options import EngineOptions
+    lib, fields = _lib.lib, [f[0] for f in _lib.XwSwitches._fields_]
+
+    def get():
+        s = _lib.XwSwitches()
+        assert lib.xw_switches_get(ctypes.byref(s)) == 0
+        return tuple(getattr(s, f) for f in fields)
+
+    def put(values):
+        return lib.xw_switches_set(ctypes.byref(_lib.XwSwitches(*values)))
+
+    ints = lambda o: tuple(int(getattr(o, f)) for f in fields)          # noqa: E731
+    # the initialiser in the one translation unit that holds the value = the defaults of the options object
+    text = open(os.path.join(ROOT, 'xnode_wan_pde_solver_amd', 'csrc', 'xw_switches.hip')).read()
+    init = re.search(r'XwSwitches switches = \{([^}]*)\};', text).group(1)
+    assert tuple(int(v) for v in init.split(',')) == ints(EngineOptions()) == (1, 1, 1, 1, 0, 1024)
+    # after load: what from_env() gives (with no variable set, those defaults)
+    start = get()
+    assert start == ints(EngineOptions.from_env())
+    assert KN.switches() == {f: getattr(EngineOptions.from_env(), f) for f in fields + ['lone_narrow']}
+    try:
+        for values in ((0, 0, 0, 0, 1024, 256), (1, 0, 1, 0, 1, 512), (0, 1, 0, 1, 0, 1024)):
+            assert put(values) == 0 and get() == values
+        keep = (1, 0, 1, 0, 7, 512)
+        assert put(keep) == 0
+        refused = [keep[:i] + (v,) + keep[i + 1:] for i in range(4) for v in (-1, 2)]
+        refused += [keep[:4] + (b, 512) for b in (-1, 1025)] + [keep[:5] + (t,) for t in (0, 128, 255, 768, 2048)]
+        assert lib.xw_switches_set(None) == -2 and lib.xw_switches_get(None) == -2 and get() == keep
+        for values in refused:
+            assert put(values) == -2 and get() == keep, values
+    finally:
+        assert put(start) == 0
+    # kernels.switched: the block's values inside, the previous ones behind it, also when the block raises
+    before = KN.switches()
+    with pytest.raises(ZeroDivisionError):
+        with KN.switched(duo_spread=False, reduce_blocks=3, reduce_threads=256, lone_narrow=False):
+            assert KN.switches() == dict(before, duo_spread=False, reduce_blocks=3, reduce_threads=256, lone_narrow=False)
+            assert get() == start[:3] + (0, 3, 256)
+            1 / 0
+    assert KN.switches() == before and get() == start
+    with pytest.raises(TypeError):
+        with KN.switched(use_graphs=False):
+            pass
+    with pytest.raises(_lib.XnwanError):
+        with KN.switched(reduce_threads=100):
+            pass
+    assert KN.switches() == before and get() == start
+    # every field is an EngineOptions field, so plan()'s options_not_at_their_defaults shows it
+    assert set(before) <= {f.name for f in dataclasses.fields(EngineOptions)}
+    # the header: its names are SWITCH_SIGNATURES, exported; the struct's fields in the mirror's order
+    hdr = open(os.path.join(ROOT, 'include', 'xnwan_switches.h')).read()
+    assert set(re.findall(r'^\s*int\s+(xw_\w+)\s*\(', hdr, flags=re.M)) == set(_lib.SWITCH_SIGNATURES)
+    out = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert set(_lib.SWITCH_SIGNATURES) <= set(re.findall(r'\bT\s+(xw_\w+)', out))
+    body = re.search(r'typedef struct \{([^}]*)\}\s*XwSwitches\s*;', hdr).group(1)
+    assert [n.strip() for n in re.sub(r'^\s*int\b', '', body.strip().rstrip(';')).split(',')] == fields

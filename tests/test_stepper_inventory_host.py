@@ -74,4 +74,3 @@ def test_oracle_spread_table_still_holds():
             assert s_ < tol / 8 and g_ < tol / 8, (c, stored, got)
             assert g_ <= 16 * s_ and s_ <= 16 * max(g_, 1e-17), (c, stored, got)
         assert T._tolerances(c) == (T.TOL_VALUE, T.TOL_GRAD, T.TOL_GRAD)
-    assert T._atoi('0') == T._atoi('00') == T._atoi('off') == 0 and T._atoi(' 1') == 1 and T._atoi('2x') == 2

@@ -30,8 +30,8 @@ A case (Launch) is what a caller of kernels.disc_xproj / disc_fwd / disc_bwd / d
                 'gradx'  disc_gradx (the recomputing kernel at W = 50, q = 9; elsewhere the forward's fused gradient)
     family      'mfma' (the C entry points xw_disc_*: containers and, at any other width, the generic path) or 'tiled'
     W, q, d, N, L, mode ('path' | 'point': L = 1, a time per point), record, xproj (a table is passed; path mode), max_blocks
-    (0: the default cap), ngrad, want_vt, and the three process-wide switches XW_DISC_VIN_LDS, XW_DISC_DYNAMIC, XW_DISC_REC_TSUM as
-    booleans (True: the default, the variable unset)
+    (0: the default cap), ngrad, want_vt, and the three library switches disc_vin_lds, disc_dynamic, disc_rec_tsum (SWITCHES) as
+    booleans (True: the default)
 """
 import collections
 import os
@@ -44,7 +44,9 @@ from stepper_inventory import ROOT, isa_same  # noqa: E402,F401
 
 CONTAINERS = (50, 64, 96, 128)                               # kernels.DISC_WIDTHS (asserted by the host test)
 QMAX = 16                                                    # XW_QMAX: deepest network with the fused input gradient (MFMA, generic)
-SWITCHES = {'vin_lds': 'XW_DISC_VIN_LDS', 'dynamic': 'XW_DISC_DYNAMIC', 'rec_tsum': 'XW_DISC_REC_TSUM'}
+# a case's attribute -> the field of options.EngineOptions (kernels.switched takes it), and the field's variable for ids and messages
+SWITCHES = {'vin_lds': 'disc_vin_lds', 'dynamic': 'disc_dynamic', 'rec_tsum': 'disc_rec_tsum'}
+ENV = {field: 'XW_' + field.upper() for field in SWITCHES.values()}
 
 _NAME = re.compile(r'(?<![\w])(k_disc_fwd|k_disc_rec|k_disc_bwd|k_disc_xproj|k_dt_fwd|k_dt_bwd|kg_disc_fwd|kg_disc_bwd)(?:<([^<>]*)>)?\(')
 _FAMILY = {'k_disc_fwd': ('fwd', 4), 'k_disc_rec': ('rec', 4), 'k_disc_bwd': ('bwd', 5), 'k_disc_xproj': ('xproj', 0),
@@ -116,7 +118,12 @@ def cid(c):
 
 def switches(c):
     """{environment variable: '0'} of the switches a case turns off"""
-    return {SWITCHES[k]: '0' for k in SWITCHES if not getattr(c, k)}
+    return {ENV[SWITCHES[k]]: '0' for k in SWITCHES if not getattr(c, k)}
+
+
+def switched_off(c):
+    """{option field: False} of the same switches: the arguments of kernels.switched for the case"""
+    return {SWITCHES[k]: False for k in SWITCHES if not getattr(c, k)}
 
 
 # ---- the dispatch, restated ---------------------------------------------------------------------------------------------------------
@@ -295,7 +302,7 @@ def reached():
 
 
 def in_process(c):
-    """True for a case that runs under the default switches (the others each need a process of their own: the switches are read once)"""
+    """True for a case that runs under the default switches (the others run inside kernels.switched(**switched_off(c)))"""
     return not switches(c)
 
 

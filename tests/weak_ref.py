@@ -40,7 +40,7 @@ VOL, KAPPA, ALPHA = 2.5, 0.7, 1e3
 # ---- the weak-form cases ---------------------------------------------------------------------------------------------------------------
 NONPAIR = ((1, 1, 1), (5, 3, 7), (37, 7, 5), (64, 6, 6), (1030, 2, 3), (4099, 33, 4), (8195, 33, 4))
 PAIR = ((1, 1, 1), (37, 1, 5), (1100, 1, 3))
-SMALL_POINTS = 4096             # shapes of at most this many points also run under XW_REDUCE_THREADS=256, XW_REDUCE_BLOCKS=3
+SMALL_POINTS = 4096             # shapes of at most this many points also run under reduce_threads=256, reduce_blocks=3
 REGIMES = ('L>d', 'L=d', 'L<d', 'pair')
 AXES = {'weight': ('path', 'point'), 'wt': (False, True), 'c': ('kappa', 'table'), 'grad': ('inline', 's3x'),
         'href': (False, True), 'bdry': ('none', 'pb1', 'pbNL', 'pbGT', 'launch'), 'final': ('none', 'kernel', 'split'),

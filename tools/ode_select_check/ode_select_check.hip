@@ -1,7 +1,8 @@
 // ode_select_check.hip -- the fused stepper's kernel selection, parent's ladders against the tables: a stand-alone host program
 // (hipcc --cuda-host-only -fsanitize=address,undefined; no GPU, no Python).  Both sides are compiled into ONE translation unit, so a
 // kernel is the same host stub on both sides and "the same kernel, template and all parameters" is pointer equality.  The launch is
-// a recorder; the CU count is the environment's FAKE_NCU (default 8); XW_DUO_SPREAD is frozen per process on both sides, so the program is run once per value.
+// a recorder; the CU count is the environment's FAKE_NCU (default 8); XW_DUO_SPREAD is frozen per process on the parent's side, and main sets
+// the library's duo_spread switch (xw_switches.hip, linked in) from the same variable, so the program is run once per value.
 //   configurations: -DXW_ODE_H=20 -DXW_ODE_K=10 | -DXW_ODE_H=64 -DXW_ODE_K=16 -DXW_ODE_WIDE16 | ... -DXW_ODE_WIDE16 -DXW_ODE_PART_RECOMP
 #include <cstdio>
 #include <cstring>
@@ -93,6 +94,11 @@ template <class T> static long slots(const T& table, const char* name) {
 int main() {
   const char* e = getenv("FAKE_NCU");
   if (e) g_ncu = atoi(e);
+  const char* sp = getenv("XW_DUO_SPREAD");
+  XwSwitches sw;
+  xw_switches_get(&sw);
+  sw.duo_spread = (sp ? atoi(sp) : 1) != 0;      // (as the parent's ladders read it)
+  if (xw_switches_set(&sw) != 0) return 2;
   const int ncu = g_ncu > 0 ? g_ncu : 8;
   const int tile_counts[] = {ncu - 1, ncu, ncu + 1, 2 * ncu - 1, 2 * ncu, 2 * ncu + 1};
   long missed = 0;
@@ -162,7 +168,6 @@ int main() {
           }
   missed += slots(recomp_table, "recomp_table");
 #endif
-  const char* sp = getenv("XW_DUO_SPREAD");
   printf("H=%d K=%d ncu=%d XW_DUO_SPREAD=%s: %ld cases (%ld kernel launches, %ld of them with a spacer round, %ld handed to the recomputing "
          "object, %ld errors), %ld disagreements, %ld table slots never reached\n", XW_ODE_H, XW_ODE_K, g_ncu, sp ? sp : "(unset)", n_cases,
          n_kernel, n_spacer, n_recomp, n_error, n_bad, missed);

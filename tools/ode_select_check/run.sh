@@ -12,8 +12,9 @@ F="--cuda-host-only -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize
 build() {
   name=$1; shift
   /opt/rocm/bin/hipcc $F "$@" -c ode_select_check.hip -o "$out/$name.o"
-  /opt/rocm/bin/hipcc -fsanitize=address,undefined "$out/$name.o" -o "$out/$name"
+  /opt/rocm/bin/hipcc -fsanitize=address,undefined "$out/$name.o" "$out/switches.o" -o "$out/$name"
 }
+/opt/rocm/bin/hipcc $F -c $C/xw_switches.hip -o "$out/switches.o"      # (the library's switches: main sets duo_spread through them)
 build m4 -DXW_ODE_H=20 -DXW_ODE_K=10 & p1=$!
 build m16 -DXW_ODE_H=64 -DXW_ODE_K=16 -DXW_ODE_WIDE16 -DXW_ODE_FWD_WAVES=1 & p2=$!
 build recomp -DXW_ODE_H=64 -DXW_ODE_K=16 -DXW_ODE_WIDE16 -DXW_ODE_FWD_WAVES=1 -DXW_ODE_PART_RECOMP & p3=$!

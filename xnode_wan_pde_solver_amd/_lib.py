@@ -166,6 +166,17 @@ EVAL_SIGNATURES = {
                             c_int, c_f64p, c_vp],
 }
 
+
+class XwSwitches(ctypes.Structure):       # include/xnwan_switches.h: the library's process-wide switches
+    _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
+
+
+# the extension header include/xnwan_switches.h: same conventions
+SWITCH_SIGNATURES = {
+    'xw_switches_set': [ctypes.POINTER(XwSwitches)],
+    'xw_switches_get': [ctypes.POINTER(XwSwitches)],
+}
+
 ERRORS = {-1: 'XW_E_DIMS: network widths/depths not among the compiled kernel instantiations',
           -2: 'XW_E_ARG: null pointer, non-positive size or bad enum',
           -3: 'XW_E_WORKSPACE: workspace too small',
@@ -186,7 +197,7 @@ def _load():
     # living in the other (every launch then fails with hipErrorNoDevice: build() followed by smoke() in ONE process did)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items()):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

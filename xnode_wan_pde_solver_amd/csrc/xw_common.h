@@ -13,6 +13,7 @@
 // The 16 columns are 16 Monte-Carlo paths (stepper) or 16 sample points (test network).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "xnwan_switches.h"
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 #define XW_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
@@ -312,3 +313,7 @@ static inline int xw_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
+
+// the library's switches (include/xnwan_switches.h; the value lives in xw_switches.hip): what a launch wrapper reads at each call
+// in place of an environment variable.  Hidden like every helper: the shared object exports xw_switches_set / _get only.
+__attribute__((visibility("hidden"))) const XwSwitches& xw_switches();

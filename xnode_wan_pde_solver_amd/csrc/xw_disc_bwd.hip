@@ -2,7 +2,6 @@
 // generic path, k_disc_rec of xw_disc_rec.hip and the recomputing kernel), xw_disc_gradx and xw_disc_bwd_slabs, and the
 // recomputing reverse kernel k_disc_bwd (all 4 instantiations).  xw_disc_core.h has the overview of the family.
 #include "xw_disc_core.h"
-#include <cstdlib>
 
 namespace {
 
@@ -324,8 +323,7 @@ extern "C" int xw_disc_bwd(const double* xT, const double* t, const double* tpp,
   if (q < 0 || d + 2 > 128 || ((q != 9 || W != 50) && act == nullptr)) return XW_E_DIMS;
   if ((long)N * L * 4 >= (1L << 31)) return XW_E_ARG;
   if (act != nullptr) {
-    static const bool tsum_on = [] { const char* e = getenv("XW_DISC_REC_TSUM"); return !(e && e[0] == '0'); }();
-    const RecKey k = rec_select(N, d, tpp != nullptr, tsum_on);
+    const RecKey k = rec_select(N, d, tpp != nullptr, xw_switches().disc_rec_tsum != 0);
     return xw_disc_rec_launch(W, k.ng, k.tsum, bwd_blocks((long)N * L), xT, t, tpp, phi, vbar, N, L, d, gslab, act, q, stream);
   }
   launch_recompute(false, xT, t, tpp, phi, vbar, N, L, d, gslab, nullptr, nullptr, stream);

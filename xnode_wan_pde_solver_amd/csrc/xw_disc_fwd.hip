@@ -2,7 +2,6 @@
 // ticket queue, the x-projection k_disc_xproj and their entry points.  xw_disc_core.h has the overview of the family.
 #include "xw_disc_core.h"
 #include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -514,11 +513,11 @@ extern "C" int xw_disc_fwd_xproj(const double* xT, const double* t, const double
   if (!disc_width_ok(W)) return xwg_disc_fwd(xT, t, tpp, phi, N, L, d, W, q, v, vt, gxv, gtv, ngrad, act, stream);
   if (xproj != nullptr && tpp != nullptr) return XW_E_ARG;             // (point mode: every point has its own x)
   if ((long)N * L * 4 >= (1L << 31)) return XW_E_ARG;                  // 32-bit lane offsets into the activation record
-  static const bool dyn_on = [] { const char* e = getenv("XW_DISC_DYNAMIC"); return !(e && e[0] == '0'); }();
   static unsigned int* qbase = [] { void* p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(xw_disc_queue)); return (unsigned int*)p; }();
   static std::atomic<unsigned int> next_slot[2];        // [0]: eager launches, [1]: launches recorded into a graph
-  static const bool vin_on = [] { const char* e = getenv("XW_DISC_VIN_LDS"); return !(e && e[0] == '0'); }();
-  const FwdKey k = fwd_select(W, ((long)N * L + 15) / 16, d, max_blocks, xproj != nullptr, dyn_on && qbase != nullptr, vin_on);
+  const XwSwitches& sw = xw_switches();
+  const FwdKey k = fwd_select(W, ((long)N * L + 15) / 16, d, max_blocks, xproj != nullptr, sw.disc_dynamic != 0 && qbase != nullptr,
+                              sw.disc_vin_lds != 0);
   // every ticketed launch takes the next queue slot: launches that can overlap in time never share one
   unsigned int* queue = nullptr;
   if (k.dyn) {

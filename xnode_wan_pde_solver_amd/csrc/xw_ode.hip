@@ -494,20 +494,15 @@ template <int M, int SLOT> struct SweepAt {
 };
 const auto sweep_table = kernel_table<SweepAt, BwdJobs, XW_SWEEP_SLOTS>();
 #ifndef XW_ODE_WIDE16     // (the wide container's duo sweep: one block per tile, no spacer round, spread = 0)
-// the switch of the duo sweep's spacer round (XW_DUO_SPREAD, default 1) and the chip's CU count: read at the first duo launch of this
-// object, then frozen for the process
-struct DuoPlacement {
-  bool spread_on;
-  int ncu;
-};
-const DuoPlacement& duo_placement() {
-  static const DuoPlacement p = [] {
-    const char* e = getenv("XW_DUO_SPREAD");
+// the chip's CU count for the duo sweep's placement: read at the first duo launch of this object, then frozen for the process (the
+// switch of the spacer round, duo_spread of xnwan_switches.h, is read at every duo launch)
+int duo_placement() {
+  static const int ncu = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    return DuoPlacement{(e ? atoi(e) : 1) != 0, n};
+    return n;
   }();
-  return p;
+  return ncu;
 }
 #endif
 #else
@@ -571,8 +566,7 @@ extern "C" int XW_ODE_FN(xw_ode_bwd_multi_w)(const XwOdeBwdJob* jobs, int njobs,
   const dim3 block(c.kind == SWEEP_DUO ? XW_DUO_THREADS : c.kind == SWEEP_N4 ? 256 : 64);
 #ifndef XW_ODE_WIDE16
   if (c.kind == SWEEP_DUO) {
-    const DuoPlacement& place = duo_placement();
-    const DuoGrid g = duo_grid(tiles, place.ncu, place.spread_on);
+    const DuoGrid g = duo_grid(tiles, duo_placement(), xw_switches().duo_spread != 0);
     J.spread = g.spread;
     grid = dim3(g.blocks);
   }

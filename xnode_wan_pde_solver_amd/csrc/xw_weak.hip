@@ -381,16 +381,13 @@ __global__ void __launch_bounds__(1024) k_slab_sum(const double* __restrict__ gs
 // the blocks of such a launch finish together: 512 blocks of 256 threads queued for ~6 us on that word (one word serves ~88
 // atomics per us) in a kernel that is on the critical path of every sub-step.  128 blocks of 1024 threads: 17.2 -> 11.3 us
 // for the 131,072 points of the headline group, 0.4794 -> 0.4717 ms per sub-step (tools/cap_sweep.sh; 256 x 512: 12.4 us, 64 x 1024: 12.5,
-// 32 x 1024: 15).  XW_REDUCE_BLOCKS / XW_REDUCE_THREADS override (measurements).
+// 32 x 1024: 15).  The switches reduce_blocks / reduce_threads (xnwan_switches.h) override (measurements).
 inline int reduce_cap(long points) {
-  static const int v = [] { const char* e = getenv("XW_REDUCE_BLOCKS"); const int x = e ? atoi(e) : 0; return x > 0 && x <= 1024 ? x : 0; }();
+  const int v = xw_switches().reduce_blocks;
   // (a million points and more -- BASELINE configs[2], [3] whole on one GPU -- stream through 256 blocks faster: 62 against 85 us at 2 M)
   return v ? v : (points > (1L << 18) ? 256 : 128);
 }
-inline int reduce_threads() {
-  static const int v = [] { const char* e = getenv("XW_REDUCE_THREADS"); const int x = e ? atoi(e) : 0; return (x == 256 || x == 512) ? x : 1024; }();
-  return v;
-}
+inline int reduce_threads() { return xw_switches().reduce_threads; }
 inline int blocks_for(long n, int per, int cap) {
   long b = (n + per - 1) / per;
   if (b < 1) b = 1;

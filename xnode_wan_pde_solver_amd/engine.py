@@ -164,6 +164,7 @@ class Engine:
         # every switch comes from ONE object (options.EngineOptions; the XW_* environment is read once, in from_env()); the
         # attributes below are the working copies -- tests and tools set them directly
         opt = self.options = options if options is not None else EngineOptions.from_env()
+        KN.apply_switches(opt)          # the library's process-wide switches: this engine's, until another one is built (options.py)
         self.d = setup['dim']
         self.method = KN.method_id(config['solver'])
         # solver 'dopri5' (DESIGN 8): every forward reads its step controllers back to the host between chunks of attempts, so

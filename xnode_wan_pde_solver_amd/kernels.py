@@ -3,9 +3,16 @@ shape) BEFORE a kernel is enqueued, then passed as a raw device pointer together
 
 Conventions (include/xnwan.h): point arrays are time-major [L, N]; coordinates are transposed xT[d, N]; all float64.
 """
+import contextlib
+import ctypes
+import dataclasses
+import types
+
 import torch
 
-from ._lib import lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob
+from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
+                   XwSwitches)
+from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
 DOPRI5 = 3                                 # solver 'dopri5' (adaptive, dopri5_fwd / dopri5_sweep below): not a fixed-grid method id
@@ -26,7 +33,46 @@ def _need_gpu():
 # Everything reachable from user code -- the module call surface, the custom operators, the first launch of every captured
 # graph -- stays checked.
 TRUSTED = False
-LONE_NARROW = __import__('os').environ.get('XW_LONE_NARROW', '1') == '1'     # (ode_fwd below)
+
+
+# ---- the library switches (options.py: the last block of EngineOptions; include/xnwan_switches.h) --------------------------------
+LIB_SWITCHES = tuple(name for name, _ in XwSwitches._fields_)     # the six the C library holds; lone_narrow is ode_fwd's, below
+_lone_narrow = True
+
+
+def apply_switches(opt):
+    """set the process-wide switches from `opt` (an EngineOptions, or anything with the seven fields); the last call wins"""
+    global _lone_narrow
+    sw = XwSwitches(*(int(getattr(opt, name)) for name in LIB_SWITCHES))
+    check(lib.xw_switches_set(ctypes.byref(sw)), 'xw_switches_set')
+    _lone_narrow = bool(opt.lone_narrow)
+
+
+def switches():
+    """{field: value} of the seven as they stand, the library's six read back from the library"""
+    sw = XwSwitches()
+    check(lib.xw_switches_get(ctypes.byref(sw)), 'xw_switches_get')
+    kinds = {f.name: f.type for f in dataclasses.fields(EngineOptions)}       # (bool for the flags, int for the two numbers)
+    out = {name: kinds[name](getattr(sw, name)) for name in LIB_SWITCHES}
+    out['lone_narrow'] = _lone_narrow
+    return out
+
+
+@contextlib.contextmanager
+def switched(**fields):
+    """`with switched(duo_spread=False): ...` -- the named switches changed for the block, the previous values back behind it"""
+    before = switches()
+    unknown = set(fields) - set(before)
+    if unknown:
+        raise TypeError('not a library switch: %s' % sorted(unknown))
+    apply_switches(types.SimpleNamespace(**dict(before, **fields)))
+    try:
+        yield
+    finally:
+        apply_switches(types.SimpleNamespace(**before))
+
+
+apply_switches(EngineOptions.from_env())
 
 
 def _chk(t, dtype, shape, name):
@@ -202,7 +248,7 @@ def ode_fwd(xT, t, start, theta, method, H, K, m, want_Y=True, u=None, Y=None):
     if Y is None and want_Y:
         Y = torch.empty(L, H, N, dtype=F64, device=xT.device)
     _chk(u, F64, (L, N), 'u'); _chk(Y, F64, (L, H, N), 'Y')
-    if Y is None and LONE_NARROW and (N + 15) // 16 <= 256 and (H, K) in ODE_WIDTHS:
+    if Y is None and _lone_narrow and (N + 15) // 16 <= 256 and (H, K) in ODE_WIDTHS:
         # an evaluation on its own (the diagnostic, a stop hook, Engine.predict) has the chip to itself: up to 256 tiles the narrow
         # layout -- four waves of 4 paths per tile, every SIMD busy -- ends sooner (57 against 73 us at 4096 paths x 32 times,
         # 109 against 143 at 64 times; beyond 256 tiles it loses: tools/lone_forward.py).  Same values to the last bit or two.

@@ -1,10 +1,20 @@
 """EngineOptions -- every switch of the engine and of train()'s loops in ONE object.
 
-The process environment (XW_* variables) is read in exactly one place, `EngineOptions.from_env()`, once, when a solver (or a
-bare Engine) is built; the object is handed down (NODE_WAN_solver.options -> Engine.options), printed by `solver.plan()`, and
-tests / tools set its FIELDS (`EngineOptions(use_graphs=False)`, `dataclasses.replace(opts, xproj_min_d=1)`) instead of
-patching the environment of the process.  The defaults are the measured optima of the headline workload (the comments in
-engine.py next to where each field is used say where they come from)."""
+The XW_* variables of the fields below are read in exactly one place, `EngineOptions.from_env()`: when a solver (or a bare
+Engine) is built, and once when `kernels` is imported.  The object is handed down (NODE_WAN_solver.options -> Engine.options),
+printed by `solver.plan()`, and tests / tools set its FIELDS (`EngineOptions(use_graphs=False)`,
+`dataclasses.replace(opts, xproj_min_d=1)`) instead of patching the environment of the process.  The defaults are the measured
+optima of the headline workload (the comments in engine.py next to where each field is used say where they come from).
+
+The library switches (the last block of fields) are process-wide: the C library holds one value (include/xnwan_switches.h) and
+reads no environment variable itself.  `kernels.apply_switches(options)` sets it in exactly two places -- when `kernels` is
+imported, from `from_env()` (so that a tool without an engine that sets the variables behaves as it always did), and in
+`Engine.__init__`, from the engine's own options.  The last applied value wins: two engines of one process with different
+library switches both run under the later one's.  `kernels.switched(...)` changes them for a `with` block (tests).
+
+Outside this object, each for its reason: XW_LIBRARY (_lib.py: read before the library is loaded); XW_DIST_BACKEND, WORLD_SIZE
+and LOCAL_RANK (dist.py: the process group is set up before any engine exists); XW_NATIVE_RNG (sampling.py: host sampling, no
+engine in reach); and the variables of bench.py's own command line."""
 import dataclasses
 import os
 from typing import Optional
@@ -75,6 +85,15 @@ class EngineOptions:
     # ---- several GPUs (dist.World) ------------------------------------------------------------------------------------------
     replicate_below: int = 16           # XW_REPLICATE_BELOW: groups with fewer paths per rank are computed whole on every rank
     native_allreduce: bool = True       # XW_NATIVE_ALLREDUCE: the exchange through xw_allreduce (RCCL) instead of torch.distributed
+    # ---- library switches: process-wide (kernels.apply_switches; the module docstring) ---------------------------------------
+    disc_dynamic: bool = True           # XW_DISC_DYNAMIC: the test network's forward deals its tiles from ticket queues (off: a static split)
+    disc_vin_lds: bool = True           # XW_DISC_VIN_LDS: ... keeps the input layer's fragments in LDS at widths 50 and 64 (off: global loads)
+    disc_rec_tsum: bool = True          # XW_DISC_REC_TSUM: the reverse pass sums the input layer's gradient once per 64-path group on vertical
+                                        # paths -- off changes that sum's order and so dVin's last bits: the same on every rank, or the replicas part
+    duo_spread: bool = True             # XW_DUO_SPREAD: the duo sweep's spacer round of empty blocks between its rounds of tiles
+    reduce_blocks: int = 0              # XW_REDUCE_BLOCKS: block cap of the deterministic grid sums, 1..1024 (0: by size -- 128, or 256 above 2^18 points)
+    reduce_threads: int = 1024          # XW_REDUCE_THREADS: their block size, 256, 512 or 1024
+    lone_narrow: bool = True            # XW_LONE_NARROW: narrow stepper tiles for a lone kernels.ode_fwd that keeps no state (module calls)
 
     @classmethod
     def from_env(cls):
@@ -124,6 +143,15 @@ class EngineOptions:
         o.dopri5_stepper = os.environ.get('XW_DOPRI5_STEPPER') or o.dopri5_stepper
         o.replicate_below = _int('XW_REPLICATE_BELOW', o.replicate_below)
         o.native_allreduce = _flag('XW_NATIVE_ALLREDUCE', o.native_allreduce)
+        o.disc_dynamic = _flag('XW_DISC_DYNAMIC', o.disc_dynamic)
+        o.disc_vin_lds = _flag('XW_DISC_VIN_LDS', o.disc_vin_lds)
+        o.disc_rec_tsum = _flag('XW_DISC_REC_TSUM', o.disc_rec_tsum)
+        o.duo_spread = _flag('XW_DUO_SPREAD', o.duo_spread)
+        # (values the launch shapes cannot take fall back to the defaults, as they always did)
+        blocks, threads = _int('XW_REDUCE_BLOCKS', o.reduce_blocks), _int('XW_REDUCE_THREADS', o.reduce_threads)
+        o.reduce_blocks = blocks if 1 <= blocks <= 1024 else 0
+        o.reduce_threads = threads if threads in (256, 512) else 1024
+        o.lone_narrow = _flag('XW_LONE_NARROW', o.lone_narrow)
         return o
 
     def non_default(self):
