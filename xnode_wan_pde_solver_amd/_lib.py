@@ -39,6 +39,11 @@ class XwPathsDopriJob(ctypes.Structure):  # include/xnwan_eval.h: one group of x
                 ('n_att', c_vp), ('Y', c_vp), ('rec', c_vp), ('fin', c_vp), ('N', c_int), ('cap', c_int)]
 
 
+class XwPathsGradJob(ctypes.Structure):   # include/xnwan_grad.h: one ragged group of xw_paths_tiled_grad (the sweep behind XwPathsJob)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('tT', c_vp), ('nstep', c_vp), ('Y', c_vp), ('gx', c_vp), ('gs', c_vp), ('ut', c_vp),
+                ('N', c_int)]
+
+
 class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
     _fields_ = [('xT', c_vp), ('start', c_vp), ('u', c_vp), ('Y', c_vp), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp),
                 ('fbuf', c_vp), ('ctl', c_vp), ('work', c_vp), ('N', c_int), ('cap', c_int)]
@@ -166,6 +171,12 @@ EVAL_SIGNATURES = {
                             c_int, c_f64p, c_vp],
 }
 
+# the extension header include/xnwan_grad.h: same conventions
+GRAD_SIGNATURES = {
+    'xw_paths_tiled_grad_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_tiled_grad': [ctypes.POINTER(XwPathsGradJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p, c_vp],
+}
+
 
 class XwSwitches(ctypes.Structure):       # include/xnwan_switches.h: the library's process-wide switches
     _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
@@ -197,7 +208,8 @@ def _load():
     # living in the other (every launch then fails with hipErrorNoDevice: build() followed by smoke() in ONE process did)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items()):
+    for name, argtypes in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(GRAD_SIGNATURES.items())
+                           + list(SWITCH_SIGNATURES.items())):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

@@ -11,7 +11,11 @@ none.  No gradients, no collective calls, no random numbers.
 
 Solver 'dopri5' has no grid to pack: kernels.paths_dopri5_fwd (csrc/xw_tdopri_paths.hip) runs a step controller per path from
 t_in to t -- one odeint call of the reference per point -- and paths_dopri5 chunks it, with one read-back of the status words per
-chunk; evaluate_points takes it with tol = (rtol, atol)."""
+chunk; evaluate_points takes it with tol = (rtol, atol).
+
+Gradients come from evaluate_points_grad alone (behind XNODE.evaluate_grad / NODE_WAN_solver.evaluate_grad): the fixed-grid forward
+with its checkpoints kept, then kernels.tiled_paths_grad (csrc/xw_tiled_paths_grad.hip), the reverse sweep over the same ragged
+group, and the chain rule through the start value (start_gradient).  Its docstring says what its `ut` is and what it refuses."""
 import torch
 
 from . import kernels as KN
@@ -20,6 +24,7 @@ from ._lib import XnwanError
 F64 = torch.float64
 EVAL_CHUNK_PATHS = 65536                   # EngineOptions.eval_chunk_paths
 REFUSED_SOLVERS = ('dopri5', 'explicit_adams')
+EVAL_GRAD_CKPT_BYTES = 1 << 30             # evaluate_points_grad: the checkpoints Y [L, H, n] of one chunk stay below this
 
 
 def step_counts(t, t_in, T0, T, n_sub):
@@ -95,6 +100,106 @@ def paths_dopri5(xT, t_in, t_end, start, theta, H, K, m, Hn, rtol, atol, max_ste
             fin[:, lo:lo + n] = job['fin']
         words[:, lo:lo + n] = w.cpu()                        # (the chunk's one read-back: waits for its launch)
     return dict(u=u, fin=fin, status=words[0], n_acc=words[1], n_att=words[2])
+
+
+def start_gradient(h, first):
+    """dh/dx [M, d] at first = [t_in, x] ([M, 1 + d]): torch.autograd.grad of h(first).sum() with respect to a leaf copy of
+    `first`, the time column dropped.  h is taken to act POINT BY POINT -- row i of its output depends on row i of its input alone,
+    as every shipped func_h does -- so the gradient of the sum is, row by row, the gradient of each start value.  Exact zeros where
+    h's output does not depend on its input (a constant h: no grad_fn, or an unused input)."""
+    with torch.enable_grad():
+        leaf = first.detach().clone().requires_grad_(True)
+        out = h(leaf)
+        if not (torch.is_tensor(out) and out.requires_grad):
+            return torch.zeros_like(first[:, 1:])
+        grad, = torch.autograd.grad(out.sum(), leaf, allow_unused=True)
+    if grad is None:
+        return torch.zeros_like(first[:, 1:])
+    return grad[:, 1:].detach().to(first.dtype)
+
+
+def grad_chunk_paths(chunk, L, H):
+    """paths per launch of evaluate_points_grad: the checkpoints Y [L, H, n] of a chunk stay below EVAL_GRAD_CKPT_BYTES (whole
+    16-path tiles, at least one) -- a memory bound, not a tuned number"""
+    return min(chunk, max(16, 16 * (EVAL_GRAD_CKPT_BYTES // (8 * L * H * 16))))
+
+
+def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta, its gradient in x and its time derivative at points [M, 1 + d] (time first; host or device, float32 or float64)
+    -> dict(u [M], grad [M, d], ut [M]), float64 on `device`.  Entry rule, step counts, packing and sort are evaluate_points';
+    per chunk kernels.tiled_paths_fwd keeps the checkpoints and kernels.tiled_paths_grad walks them back:
+      u     the forward's last row: the bits of evaluate_points
+      grad  du/dx of the DISCRETE solution with every point's grid held fixed: gx + gs * dh/dx (start_gradient: the chain rule
+            through the start value h([T0, x]))
+      ut    FL_w . F(t, x, y(t)): the time derivative of the CONTINUOUS model y' = F, u = FL y at fixed x -- not the derivative
+            of the discrete u with respect to the end time of its grid (that would need the derivative of the steps in dt).
+    Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, and every point that is not
+    entered at T0 -- the hourglass's re-entered points, whose entry time |x| / r depends on x: holding it fixed would not give the
+    gradient.  No collective calls, no random numbers."""
+    if solver in REFUSED_SOLVERS:
+        raise XnwanError("evaluate_grad(): solver %r is not served -- the reverse sweep over per-path time grids runs the fixed-grid "
+                         "schemes %s only (it reverses the steps taken; no per-path step controller or multistep history is built)"
+                         % (solver, sorted(KN.METHODS)))
+    entry = getattr(domain, 'entry', None)
+    if entry is None:
+        name = getattr(domain, '__name__', type(domain).__name__)
+        raise XnwanError('evaluate_grad(): the domain class %s has no entry(points, shape_param, T0, T) rule: where a point\'s path '
+                         'starts, and with which start value, is the domain\'s to say' % name)
+    d, T0, T = setup['dim'], setup['T0'], setup['T']
+    n_sub = setup['N_t'] if n_sub is None else n_sub
+    if n_sub < 1:
+        raise XnwanError('evaluate_grad(): n_sub = %r, at least one step over [T0, T]' % (n_sub,))
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 1 + d):
+        raise XnwanError('evaluate_grad(): points must be a tensor [M, 1 + d] = [M, %d], time first' % (1 + d))
+    with torch.no_grad():
+        pts = points.detach().to(F64)
+        M = pts.shape[0]
+        if M == 0:
+            return dict(u=torch.empty(0, dtype=F64, device=device), grad=torch.empty(0, d, dtype=F64, device=device),
+                        ut=torch.empty(0, dtype=F64, device=device))
+        t = pts[:, 0].contiguous()
+        t_in, at_T0 = entry(pts, setup['shape_param'], T0, T)
+        early = t < t_in
+        if bool(early.any()):
+            i = int(early.nonzero()[0])
+            raise XnwanError('evaluate_grad(): %d points lie before their entry time (t >= t_in is the limit; first: point %d, '
+                             't = %r, t_in = %r)' % (int(early.sum()), i, float(t[i]), float(t_in[i])))
+        late = ~at_T0
+        if bool(late.any()):
+            i = int(late.nonzero()[0])
+            raise XnwanError('evaluate_grad(): %d points are not entered at T0 (entry at T0 is the limit; first: point %d, t = %r, '
+                             't_in = %r): their path starts on the moving boundary at a time that depends on x, and a gradient '
+                             'with that time held fixed is not du/dx' % (int(late.sum()), i, float(t[i]), float(t_in[i])))
+        first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
+        s = h(first).reshape(-1).double()
+        hx = start_gradient(h, first).to(F64)
+        n = step_counts(t, t_in, T0, T, n_sub)
+        order, inverse = sort_by_steps(n)
+        tT = pack_grids(t[order], t_in[order], n[order]).to(device)
+        xT = pts[order, 1:].t().contiguous().to(device)
+        start, nstep = s[order].contiguous().to(device), n[order].to(torch.int32).to(device)
+        L = tT.shape[0]
+        per = grad_chunk_paths(chunk, L, H)
+        u = torch.empty(M, dtype=F64, device=device)
+        gx = torch.empty(d, M, dtype=F64, device=device)
+        gs, ut = torch.empty(M, dtype=F64, device=device), torch.empty(M, dtype=F64, device=device)
+        for lo in range(0, M, per):
+            k = min(lo + per, M) - lo
+            whole = k == M
+            job = dict(xT=xT if whole else xT[:, lo:lo + k].contiguous(), start=start[lo:lo + k],
+                       tT=tT if whole else tT[:, lo:lo + k].contiguous(), nstep=nstep[lo:lo + k],
+                       u=torch.empty(L, k, dtype=F64, device=device), Y=torch.empty(L, H, k, dtype=F64, device=device))
+            KN.tiled_paths_fwd([job], theta, method, H, K, m)
+            out = dict(gx=gx if whole else torch.empty(d, k, dtype=F64, device=device), gs=gs[lo:lo + k], ut=ut[lo:lo + k])
+            KN.tiled_paths_grad([dict(job, **out)], theta, method, H, K, m)
+            u[lo:lo + k] = job['u'][L - 1]
+            if not whole:
+                gx[:, lo:lo + k] = out['gx']
+        inv = inverse.to(device)
+        grad = gx.t()[inv] + gs[inv].view(-1, 1) * hx.to(device)
+        return dict(u=u[inv], grad=grad.contiguous(), ut=ut[inv])
 
 
 def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS, tol=None,

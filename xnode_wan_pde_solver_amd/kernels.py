@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwSwitches)
+                   XwPathsGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -495,6 +495,38 @@ def tiled_paths_fwd(jobs, theta, method, H, K, m, last_only=False):
     # (xw_paths_tiled_work is the forward workspace of the family, xw_tiled_ode_work(0, ...): one allocation helper for both)
     work = tiled_ode_work(False, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), theta.device)
     check(lib.xw_paths_tiled_fwd(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_fwd')
+
+
+def tiled_paths_grad(jobs, theta, method, H, K, m):
+    """the reverse sweep behind tiled_paths_fwd (csrc/xw_tiled_paths_grad.hip, include/xnwan_grad.h): job = dict(xT[d,N], start[N],
+    tT[L,N], optional nstep[N] int32 -- as the forward pass took them --, Y[L,H,N], the checkpoints that forward pass wrote (not
+    last_only), and the outputs asked for, at least one of gx[d,N], gs[N], ut[N]).  With the cotangent 1 on every path's final value
+    u_p: gx = du_p/dx_p and gs = du_p/dstart_p, the discrete adjoint (the exact reverse of the steps taken, grid and step sizes held
+    fixed); ut = FL_w . F(t_p, x_p, y(t_p)), the time derivative of the CONTINUOUS model at fixed x -- not the derivative of the
+    discrete u with respect to the end of its grid.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsGradJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        if j.get('Y') is None:
+            raise XnwanError('tiled_paths_grad: Y [L, H, N], the checkpoints of tiled_paths_fwd, is needed (the forward is not recomputed)')
+        _chk(j['Y'], F64, (L, H, N), 'Y')
+        if j.get('gx') is None and j.get('gs') is None and j.get('ut') is None:
+            raise XnwanError('tiled_paths_grad: no output requested (at least one of gx, gs, ut)')
+        _chk(j.get('gx'), F64, (d, N), 'gx'); _chk(j.get('gs'), F64, (N,), 'gs'); _chk(j.get('ut'), F64, (N,), 'ut')
+        a.xT, a.start, a.tT, a.nstep, a.Y = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep')), _p(j['Y'])
+        a.gx, a.gs, a.ut, a.N = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('ut')), N
+    # (xw_paths_tiled_grad_work is the sweep workspace of the family, xw_tiled_ode_work(1, ...): one allocation helper for both)
+    work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), theta.device)
+    check(lib.xw_paths_tiled_grad(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_grad')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

@@ -340,6 +340,26 @@ class XNODE(nn.Module):
                                              self.method, self.kdims[0], self.kdims[1], self.num_layers, dev,
                                              chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk, **adaptive)
 
+    def evaluate_grad(self, points, n_sub=None, chunk=None):
+        """u_theta, its gradient in x and its time derivative at scattered space-time points [M, 1 + d] (time first; host or
+        device) -> dict(u [M], grad [M, d], ut [M]) on the network's device, in one launch chain per chunk
+        (evalpaths.evaluate_points_grad): evaluate()'s grids, the forward with its checkpoints kept, the reverse sweep over them.
+        u: the bits of evaluate().  grad: du/dx of the discrete solution, every point's grid held fixed, the chain rule through the
+        start value h([T0, x]) included (h is differentiated by autograd and taken to act point by point).  ut: FL_w . F(t, x, y(t)),
+        the time derivative of the CONTINUOUS model at fixed x -- not the derivative of the discrete u with respect to the end time
+        of its grid.  Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, and points that
+        are not entered at T0 (the hourglass's re-entered points: their entry time depends on x).  chunk: paths per launch
+        (evalpaths.EVAL_CHUNK_PATHS, bounded further by the checkpoints' memory, evalpaths.EVAL_GRAD_CKPT_BYTES)."""
+        from . import evalpaths
+        if self.blob is None:
+            raise XnwanError('XNODE.bind(device) has not been called')
+        self.blob.check_alias()
+        dev = self.blob.data.device
+        with torch.cuda.device(dev):
+            return evalpaths.evaluate_points_grad(points, n_sub, self.setup, self.domain, self.solver, self.h, self.blob.data,
+                                                  self.method, self.kdims[0], self.kdims[1], self.num_layers, dev,
+                                                  chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk)
+
     def forward(self, inputs, starts_at_T0=None):
         """starts_at_T0 (optional): the caller knows where the paths start -- True: at T0 (start values h), False: on the
         moving boundary (start values g; the sampler's late-entry groups).  Saves reading inputs[0, 0, 0] / max(w) back from the
