@@ -607,7 +607,7 @@ def test_engine_options_are_read_from_the_environment_once_and_in_one_place(monk
         monkeypatch.setenv(var, {'XW_REDUCE_BLOCKS': '3', 'XW_REDUCE_THREADS': '256'}.get(var, '0'))
     assert EngineOptions.from_env().non_default() == dict({f: False for f in off.values()}, reduce_blocks=3, reduce_threads=256)
     pkg = os.path.join(ROOT, 'xnode_wan_pde_solver_amd')
-    for name in ('engine.py', 'solver.py', 'kernels.py'):
+    for name in ('engine.py', 'groups.py', 'solver.py', 'kernels.py'):
         assert 'os.environ' not in open(os.path.join(pkg, name)).read(), name
     # ... and the C library reads none: its switches are set through include/xnwan_switches.h
     csrc = os.path.join(pkg, 'csrc')

@@ -6,6 +6,7 @@ Layout:
     kernels.py   tensor-level wrappers: shape / dtype checks, stream plumbing
     nets.py      parameter blobs + nn.Module shells with the reference's state_dict keys
     sampling.py  Hypercube / sphere domains and the loader (host RNG parity with the reference)
+    groups.py    loading a sample into the engine's groups (Group, the four loaders: the base class of Engine)
     engine.py    the fused generator / discriminator step (graph-capturable)
     dist.py      path sharding + the RCCL exchange of the scalar partials and packed gradients
 """

@@ -13,26 +13,18 @@ Semantics are the reference's ON A GPU, stated once here 
   Q4  v is evaluated on its own interior sample XV;
   Q5  no stale .grad carry-over between sub-steps (that is a CPU-only artefact of the reference).
 
-Data layout in HBM (per group of N equal-length paths, L sample times, d dimensions):
-  xT, xvT, xbT  float64 [d, N]   transposed coordinates of the u-, v- and boundary samples (the [N, L, d+1] path tensor
-                                 of the reference is never materialised on the device: on vertical paths it is x (x) t)
-  t             float64 [L]      shared time grid
-  u, v, vt, f, ubar, vbar ...    float64 [L, N]   time-major point arrays (coalesced for one-lane-per-path kernels)
-  Y             float64 [L, H, N]  hidden-state checkpoints of the stepper (written by the forward, read by the sweeps)
-  act, act_b    float64 [L-1, rows, N]   stage activations of every step (forward -> sweeps: no field re-evaluation)
-  vact          float64 [(q+1) W, N L]   layer inputs of the test network (its forward -> its backward)
-  slabs         float64 [n_slab, P]  per-wave partial parameter gradients, summed inside the Adam kernel
+The per-sample half -- loading a sample into a Group, the data layout of a group in HBM -- is groups.py (GroupLoading, the
+base class of Engine); this file is the sub-step schedule: streams, graphs, the runner, both sub-steps and predict*.
 """
 import contextlib
-import math
-import os
 
 import torch
 
 from . import kernels as KN
 from ._lib import XnwanError
 from .options import EngineOptions
-from .sampling import HIP_HOST_LOCK, _PIN_POOL, Hypercube, _paths
+from .groups import F32, F64, Group, GroupLoading, Structure, at_T0, start_values      # noqa: F401  (Group, Structure: part of this module's surface)
+from .sampling import HIP_HOST_LOCK
 
 
 def ctypes_addr(fn):
@@ -79,86 +71,8 @@ def _scratch_pool(which=0):
         _SCRATCH_POOL.append(torch.cuda.graph_pool_handle())
     return _SCRATCH_POOL[which]
 
-F32, F64 = torch.float32, torch.float64
 
-
-def _d64(x, dev):
-    """x on `dev` as float64; the tensor itself when it already is (two no-op .to() calls cost ~8 us of host time, and a
-    list-domain sample makes ~400 of them)"""
-    if x.dtype == F64 and x.device == dev:
-        return x
-    return x.to(dev).to(F64)
-
-
-def _to_LN(x, dev):
-    """[N, L] (any float dtype, any device) -> contiguous float64 [L, N] on dev"""
-    return _d64(x.detach(), dev).t().contiguous()
-
-
-class Structure:
-    """What the PDE coefficient callables look like, found by probing them once on a few random points."""
-
-    def __init__(self, funcs, d, lo=-1.0, hi=1.0):
-        g = torch.Generator().manual_seed(20221111)
-        Xp = torch.rand(6, 3, d + 1, generator=g) * (hi - lo) + lo
-        Xp[:, :, 0] = torch.rand(6, 3, generator=g)
-        ident = True
-        for i in range(d):
-            for j in range(d):
-                a = funcs['a'](Xp, i, j)
-                if not bool(torch.all(a == (1.0 if i == j else 0.0))):
-                    ident = False
-                    break
-            if not ident:
-                break
-        self.a_identity = ident
-        self.b_zero = all(bool(torch.all(funcs['b'](Xp, i) == 0)) for i in range(d))
-        u1 = torch.randn(6, 3, 1, generator=g, dtype=F64)
-        u2 = torch.randn(6, 3, 1, generator=g, dtype=F64)
-        c1, c2 = funcs['c'](Xp, u1), funcs['c'](Xp.flip(0), u2)
-        k = (c1 / u1).reshape(-1)
-        self.c_kappa = None
-        if torch.is_tensor(c1) and c1.shape == u1.shape and bool(torch.all(k == k[0])) and bool(torch.all(c2 == k[0] * u2)):
-            self.c_kappa = float(k[0])
-
-    def describe(self):
-        return 'a=%s b=%s c=%s' % ('identity' if self.a_identity else 'general', 'zero' if self.b_zero else 'general',
-                                   ('%g*u' % self.c_kappa) if self.c_kappa is not None else 'general')
-
-
-class Group:
-    """Device-resident data of one group of equal-length paths + every buffer its sub-steps need.  Buffers are allocated
-    once and refilled in place by Engine.load_group(..., into=G), so captured HIP graphs stay valid across resampling."""
-    SAMPLE_FIELDS = ('t', 'tb', 'tpp', 'tpp0', 'xvT_pts', 'xT', 'xvT', 'xbT', 'start', 'ghT', 'h', 'href', 'f', 'w', 'wt', 'w0', 'gwx0T',
-                     'start_b', 'g', 'X', 'A0', 'B0')
-
-    def signature(self):
-        return tuple((k, tuple(getattr(self, k).shape)) for k in self.SAMPLE_FIELDS if getattr(self, k, None) is not None)
-
-    # The work buffers are regions of ONE allocation (`_arena`), described by `_lazy` = {name: (offset, shape)}; the tensor
-    # view of a region is made when somebody reads the attribute.  The sub-step runner only needs addresses (ptr): the groups
-    # of a list domain are rebuilt with every sample, 19 groups x 22 buffers, and a torch.empty or a view costs the host 4 us each.
-    def __getattr__(self, name):          # (only reached when the attribute is not set)
-        lazy = self.__dict__.get('_lazy')
-        if lazy is not None and name in lazy:
-            off, shape = lazy[name]
-            t = self.__dict__['_arena'][off:off + math.prod(shape)].view(shape)
-            self.__dict__[name] = t
-            return t
-        raise AttributeError(name)
-
-    def ptr(self, name):
-        """device address of a buffer (0: the group has none)"""
-        t = self.__dict__.get(name)
-        if t is not None:
-            return t.data_ptr()
-        lazy = self.__dict__.get('_lazy')
-        if lazy is not None and name in lazy:
-            return self.__dict__['_arena'].data_ptr() + 8 * lazy[name][0]
-        return 0
-
-
-class Engine:
+class Engine(GroupLoading):
     def __init__(self, config, setup, u_mod, v_mod, funcs, device, world=None, structure=None, options=None):
         self.config, self.setup, self.u, self.v, self.funcs, self.dev, self.world = config, setup, u_mod, v_mod, funcs, device, world
         # every switch comes from ONE object (options.EngineOptions; the XW_* environment is read once, in from_env()); the
@@ -372,645 +286,6 @@ class Engine:
                                  and opt.capture_exchange)
         if self.capture_exchange:
             world.all_reduce(self.scal)           # (zeros) first use outside any capture: RCCL sets up its channels here
-
-    # ------------------------------------------------------------------------------------------------------------
-    # coefficient tables (src/training.py:32-41).  Only time index 0 can contribute (Q3), so that slice is all that is
-    # tabulated: [d,d,N] instead of the reference's [d,d,N,L].
-    # ------------------------------------------------------------------------------------------------------------
-    def _tabulate_a(self, X1):
-        """a_ij(t_0, x_n) on the sample X1 [N,1,d+1], returned as (table, amode) -- the form is stated explicitly
-        (xw_weak_contract_general's amode), never guessed from the shape: [d,d] and [d,N] coincide when N == d.  ONE batched call of the user's callable with index tensors
-        i[d,1,1,1], j[1,d,1,1] when it is written with tensor operations (checked against scalar calls on three index
-        pairs); otherwise the reference's d^2 scalar calls.  The table is then stored in the cheapest EXACT form: one
-        [d,d] matrix if it does not vary over the sample, its diagonal [d,N] if every off-diagonal entry is exactly zero."""
-        d, dev, fa = self.d, self.dev, self.funcs['a']
-        N = X1.shape[0]
-        A = None
-        try:
-            ii = torch.arange(d, device=X1.device).view(d, 1, 1, 1)
-            jj = torch.arange(d, device=X1.device).view(1, d, 1, 1)
-            out = fa(X1.unsqueeze(0).unsqueeze(0), ii, jj)
-            if torch.is_tensor(out) and tuple(out.shape) == (d, d, N, 1):
-                A = out[..., 0].to(dev).to(F32).to(F64)       # (the reference's table is float32: src/training.py:32)
-                g = torch.Generator().manual_seed(d * 7919 + N)
-                for _ in range(3):
-                    i, j = (int(k) for k in torch.randint(0, d, (2,), generator=g))
-                    if not torch.equal(A[i, j], fa(X1, i, j).to(dev).to(F32).to(F64)[:, 0]):
-                        A = None
-                        break
-        except Exception:               # the callable branches on (i, j) in Python, indexes with them, ...: scalar calls
-            A = None
-        if A is None:
-            A = torch.stack([torch.stack([fa(X1, i, j).to(dev).to(F32).to(F64)[:, 0] for j in range(d)], 0) for i in range(d)], 0)
-        off = A.clone()
-        off.diagonal(dim1=0, dim2=1).zero_()
-        if bool(torch.all(A == A[:, :, :1])):
-            return A[:, :, 0].contiguous(), 1                          # [d, d]   one matrix for all points
-        if bool(torch.all(off == 0)):
-            return A.diagonal(dim1=0, dim2=1).t().contiguous(), 2      # [d, N]   diagonal
-        return A.contiguous(), 3                                       # [d, d, N] full table
-
-    def _tabulate_b(self, X1):
-        d, dev, fb = self.d, self.dev, self.funcs['b']
-        N = X1.shape[0]
-        try:
-            out = fb(X1.unsqueeze(0), torch.arange(d, device=X1.device).view(d, 1, 1))
-            if torch.is_tensor(out) and tuple(out.shape) == (d, N, 1):
-                B = out[..., 0].to(dev).to(F32).to(F64)       # (float32 table: src/training.py:37)
-                if all(torch.equal(B[i], fb(X1, i).to(dev).to(F32).to(F64)[:, 0]) for i in (0, d // 2, d - 1)):
-                    return B.contiguous()
-        except Exception:
-            pass
-        return torch.stack([fb(X1, i).to(dev).to(F32).to(F64)[:, 0] for i in range(d)], 0).contiguous()
-
-    def _check_structure(self, X, version):
-        """The fused fast paths (a = identity, b = 0, c = kappa u) were chosen from a probe on random points
-        (Structure).  Guard them on the ACTUAL sample, every time one is loaded: the whole diagonal of a, one rotating
-        off-diagonal per row (all pairs are visited over d samples), every b_i, and c against kappa u -- a coefficient
-        that only deviates in part of the domain raises here instead of silently training the wrong PDE."""
-        st, d = self.structure, self.d
-        X1 = X[:, :1, :]
-        bad = []                                   # (device-side flags, ONE host sync for the whole check)
-        if st.a_identity:
-            for i in range(d):
-                j = (i + 1 + version % max(d - 1, 1)) % d
-                bad.append(('func_a[%d,%d] == 1' % (i, i), torch.any(self.funcs['a'](X1, i, i) != 1)))
-                if d > 1:
-                    bad.append(('func_a[%d,%d] == 0' % (i, j), torch.any(self.funcs['a'](X1, i, j) != 0)))
-        if st.b_zero:
-            for i in range(d):
-                bad.append(('func_b[%d] == 0' % i, torch.any(self.funcs['b'](X1, i) != 0)))
-        if st.c_kappa is not None:
-            key = (tuple(X.shape[:2]), str(X.device))
-            if getattr(self, '_probe_u', (None, None))[0] != key:
-                g = torch.Generator().manual_seed(1)
-                self._probe_u = (key, torch.randn(X.shape[0], X.shape[1], 1, generator=g, dtype=F64).to(X.device))
-            up = self._probe_u[1]
-            bad.append(('func_c(X, u) == %g u' % st.c_kappa, torch.any(self.funcs['c'](X, up) != st.c_kappa * up)))
-        # (results on the host cost nothing to read; results on the device are read back together: ONE sync)
-        dev_flags = [b for _, b in bad if b.is_cuda]
-        hit = any(bool(b) for _, b in bad if not b.is_cuda) or (bool(torch.stack(dev_flags).any()) if dev_flags else False)
-        if hit:
-            which = [name for name, b in bad if bool(b)]
-            raise XnwanError('the PDE coefficients do not have the structure the probe at construction saw (%s): violated on this '
-                             'sample: %s.  Build the solver with an explicit engine.Structure.' % (st.describe(), ', '.join(which[:4])))
-
-    # ------------------------------------------------------------------------------------------------------------
-    # per-sample preparation (once per outer iteration; everything here is parameter-independent)
-    # ------------------------------------------------------------------------------------------------------------
-    def tabulate_sample(self, triples, domain, hints=None, grids=None):
-        """List domains (src/dataset.py:48-229: 11-20 groups per sample): evaluate the user's callables h, f, g and the
-        domain's weight w (with their input gradients) ONCE on the points of ALL groups instead of group by group, and
-        hand every group its slices (load_group(tab=...)).  The callables are PDE data -- functions of the point (t, x) --
-        so evaluating them on a concatenation is the same arithmetic per point; that is CHECKED on the first group of the
-        first sample (bitwise against the per-group call) and batching is switched off with a warning if it does not hold.
-        Per outer iteration this removes ~140 of ~150 callable evaluations, each a dozen tiny kernel launches."""
-        if getattr(self, '_batch_tab', True) is False or len(triples) < 2:
-            return [None] * len(triples)
-        if sum(t_[0].shape[0] for t_ in triples) == 0 or sum(t_[2].shape[0] for t_ in triples) == 0:
-            return [None] * len(triples)      # (a rank whose shares of this sample hold no interior / no boundary path at all: group by group)
-        d, T0 = self.d, self.setup['T0']
-        Xs = [t_[0].detach() for t_ in triples]
-        XVs = [t_[1].detach() for t_ in triples]
-        BXs = [t_[2].detach() for t_ in triples]
-        if hints is not None and all(h is not None for h in hints):      # (the loader read them off its host copies: no read-back)
-            first_t = [h['t0'] for h in hints] + [h['tb0'] for h in hints]
-        else:
-            # ONE host sync for all start times; a share of a sharded group reads the WHOLE group's first paths (`grids`: it may be
-            # empty, or start at another path's entry time)
-            gr = grids if grids is not None else [None] * len(Xs)
-            if any(g_ is None and (x.shape[0] == 0 or b.shape[0] == 0) for g_, x, b in zip(gr, Xs, BXs)):
-                raise XnwanError('tabulate_sample: an empty share needs the first times of the whole group (hints or grids)')
-            first_t = torch.stack([(g_[0][0] if g_ is not None else x[0, 0, 0]).to(Xs[0].device) for g_, x in zip(gr, Xs)] +
-                                  [(g_[1][0] if g_ is not None else b[0, 0, 0]).to(Xs[0].device) for g_, b in zip(gr, BXs)]).tolist()
-        at0 = [float(v) == T0 for v in first_t[:len(Xs)]]
-        bat0 = [float(v) == T0 for v in first_t[len(Xs):]]
-        pts = lambda ts: torch.cat([t_.reshape(-1, 1, d + 1) for t_ in ts], 0)                      # noqa: E731  [P, 1, d+1]
-        cuts = lambda ts: [t_.shape[0] * t_.shape[1] for t_ in ts]                                  # noqa: E731
-        f_cat = self.funcs['f'](pts(Xs)).detach().reshape(-1)
-        g_cat = self.funcs['g'](pts(BXs)).detach().reshape(-1)
-        f_all, g_all = f_cat.split(cuts(Xs)), g_cat.split(cuts(BXs))
-        XVp = pts(XVs).clone().requires_grad_(True)
-        w_all = domain.func_w(XVp)
-        gw_all = torch.autograd.grad(w_all.sum(), XVp)[0] if w_all.requires_grad else torch.zeros_like(XVp)
-        w_cat, gw_cat = w_all.detach().reshape(-1), gw_all.reshape(-1, d + 1)
-        w_all, gw_all = w_cat.split(cuts(XVs)), gw_cat.split(cuts(XVs))
-        # start values with their x-gradient: h for groups that start at T0, g for groups that start on the boundary
-        # (h is evaluated ONLY on the start points of the groups that start at T0 and g ONLY on those that start on the
-        #  boundary -- the combinations the per-group path evaluates: a callable that is not finite, or has no finite
-        #  gradient, where it is never asked must not leak a NaN into the other groups through a masked merge)
-        def starts(ts, flags):
-            P0 = torch.cat([x[:, 0, :] for x in ts], 0).clone().requires_grad_(True)
-            n = [x.shape[0] for x in ts]
-            # (the groups are contiguous row ranges of P0: the rows of the groups that start at T0 / on the boundary are taken and
-            #  put back as slices -- an index tensor would have to be uploaded or found on the device, both of which wait for
-            #  everything queued on the stream, i.e. for the previous iteration's sub-steps when this runs beside them)
-            rows = P0.split(n)
-            pick = lambda want: [r for r, a in zip(rows, flags) if a == want]                 # noqa: E731
-            rows_h, rows_g = pick(True), pick(False)
-            some = lambda rows: sum(r.shape[0] for r in rows) > 0          # noqa: E731  (a rank's shares may hold none of them)
-            hval = self.funcs['h'](torch.cat(rows_h, 0)).reshape(-1) if some(rows_h) else None
-            gval = self.funcs['g'](torch.cat(rows_g, 0).unsqueeze(1)).reshape(-1) if some(rows_g) else None
-            ref = hval if hval is not None else gval
-            none = ref.new_zeros(0)
-            it_h = iter(hval.split([r.shape[0] for r in rows_h])) if hval is not None else iter([none] * len(rows_h))
-            it_g = iter(gval.to(ref.dtype).split([r.shape[0] for r in rows_g])) if gval is not None else iter([none] * len(rows_g))
-            val = torch.cat([next(it_h) if a else next(it_g) for a in flags], 0)
-            return P0, n, val
-        X0, n0, start = starts(Xs, at0)
-        gh = torch.autograd.grad(start.sum(), X0)[0][:, 1:] if start.requires_grad else torch.zeros(X0.shape[0], d, device=X0.device, dtype=X0.dtype)
-        # h on every interior start point (the s1 term and the initial penalty read it on all groups, src/loss.py:64,79;
-        # for the groups that start at T0 it IS the start value)
-        hv = start if all(at0) else self.funcs['h'](X0.detach()).reshape(-1)
-        _, nb0, sb = starts(BXs, bat0)
-        sb = sb.detach()
-        tabs = []
-        # (the unsplit tables, for load_groups_packed: one gather launch takes every group's fields out of them)
-        self._tab_cat = dict(f=f_cat, g=g_cat, w=w_cat, gw=gw_cat, start=start.detach(), gh=gh, h=hv.detach(), start_b=sb, at0=at0, bat0=bat0)
-        start_k, gh_k, hv_k, sb_k = start.detach().split(n0), gh.split(n0), hv.detach().split(n0), sb.split(nb0)   # (once: a split is 20 new tensors)
-        for k, (x, xv, bx) in enumerate(zip(Xs, XVs, BXs)):
-            N, L = x.shape[0], x.shape[1]
-            tabs.append(dict(starts_T0=at0[k], start=start_k[k], gh=gh_k[k], h=hv_k[k],
-                             f=f_all[k].view(N, L), w=w_all[k].view(N, L), gw=gw_all[k].view(N, L, d + 1),
-                             b_T0=bat0[k], start_b=sb_k[k], g=g_all[k].view(bx.shape[0], bx.shape[1])))
-        if not getattr(self, '_batch_tab_checked', False):
-            self._batch_tab_checked = True
-            # bitwise against the per-group calls: f, h, w on the first group, and g, the start values with their gradient and the
-            # boundary start values on the LAST triple (a late group: boundary-type starts on the hourglass)
-            # (the first and the last group of which this rank holds interior AND boundary paths: an empty share has nothing to compare)
-            full = [k for k in range(len(Xs)) if Xs[k].shape[0] > 0 and BXs[k].shape[0] > 0] or [0]
-            k0, kl = full[0], full[-1]
-            x, t0 = Xs[k0], tabs[k0]
-            xl, bl, tl = Xs[kl], BXs[kl], tabs[kl]
-            eq = lambda a, b: torch.equal(a.detach().reshape(-1), b.detach().reshape(-1))      # noqa: E731
-            xl0 = xl[:, 0, :].clone().requires_grad_(True)
-            s_l = self.funcs['h'](xl0) if at0[kl] else self.funcs['g'](xl0.unsqueeze(1)).reshape(-1)
-            g_l = torch.autograd.grad(s_l.sum(), xl0)[0][:, 1:] if s_l.requires_grad else torch.zeros_like(xl0[:, 1:])
-            sb_l = self.funcs['h'](bl[:, 0, :]) if bat0[kl] else self.funcs['g'](bl[:, 0, :].unsqueeze(1))
-            if not (eq(self.funcs['f'](x), t0['f']) and eq(self.funcs['h'](x[:, 0, :]), t0['h']) and eq(domain.func_w(XVs[k0]), t0['w'])
-                    and eq(self.funcs['g'](bl), tl['g']) and eq(s_l, tl['start']) and eq(g_l, tl['gh']) and eq(sb_l, tl['start_b'])):
-                import warnings
-                warnings.warn('the PDE callables give different values on a concatenation of groups than group by group (not pointwise?): '
-                              'tabulating group by group', RuntimeWarning)
-                self._batch_tab = False
-                return [None] * len(triples)
-        return tabs
-
-    def load_group(self, X, XV, BX, domain, n_glob=None, nb_glob=None, into=None, shared_grid_t0=None, tab=None, verify=True,
-                   hints=None, grids=None):
-        """Prepare one group.  The user's callables (h, f, g, func_w, a, b) are evaluated on the device the given
-        tensors live on and only their results are uploaded: pass the loader's host tensors to tabulate exactly like
-        the reference's CPU path, or device tensors to tabulate on the GPU (float32 transcendental functions then
-        differ from the host's in the last bit).  `into`: a Group of the same shapes to refill in place.
-        `shared_grid_t0`: the caller built X, XV and BX from ONE time grid whose first time is this value (compact cube
-        samples): the checks that would otherwise read the device tensors back (four host syncs) are skipped.
-        `hints` (list domains, sampling.Comb_loader.pack): the same facts per group, read off the loader's HOST copies --
-        `shared_times` (all paths of the group share one time column), `same_grid` (the boundary group sits on the
-        interior group's grid).
-        `n_glob`, `nb_glob` (several ranks): X, XV, BX are this rank's SHARE of a group of that many interior / boundary paths --
-        the sub-steps of the group then run the exchange steps of dist.py; None: the whole group is here (one process, or a
-        group every rank computes in full, dist.World.replicated).  A share may be empty ([0, L, d+1]: a group with fewer paths
-        than ranks); `grids` = (time column of the WHOLE group's first interior path, of its first boundary path): the reference
-        integrates every path of a group on its first path's grid (src/model.py:92: inputs[0, :, 0]), which an empty share does
-        not hold and a later share holds a different one of where the paths of a group enter at their own times."""
-        dev, d = self.dev, self.d
-        sharded = n_glob is not None and self.world is not None
-        X, XV = X.detach(), XV.detach()
-        BX = BX.detach() if BX is not None else None
-        N, L = X.shape[0], X.shape[1]
-        Nb = BX.shape[0] if BX is not None else 0
-        if XV.shape[1] != L or XV.shape[0] != N:
-            raise XnwanError('u- and v-samples of a group must have the same shape')
-        if (N == 0 or (BX is not None and Nb == 0)) and not (sharded and grids is not None):
-            raise XnwanError("a group without interior or boundary paths only exists as a rank's share of a sharded group (n_glob, grids)")
-        S = {}
-        S['t'] = _d64(grids[0] if grids is not None else X[0, :, 0], dev).contiguous()
-        S['xT'] = _d64(X[:, 0, 1:], dev).t().contiguous()
-        S['xvT'] = _d64(XV[:, 0, 1:], dev).t().contiguous()
-        # the test network is pointwise on XV: when the paths of a group do not share one time column (late-entry groups
-        # of the hourglass: every path has its own entry time at l = 0) it runs in point mode on all L*N points
-        S['tpp'] = S['tpp0'] = S['xvT_pts'] = None
-        # (a share of a sharded group is compared with the WHOLE group's first path, whose grid G.t is: `grids`)
-        col0 = XV[:1, :, 0] if grids is None else grids[0].to(XV.device).view(1, -1)
-        if shared_grid_t0 is None and not (hints['shared_times'] if hints is not None else bool(torch.all(XV[:, :, 0] == col0))):
-            S['tpp'] = _d64(XV[:, :, 0], dev).t().contiguous().reshape(-1)              # time-major: p = l*N + n
-            S['tpp0'] = _d64(XV[:, 0, 0], dev).contiguous()
-            S['xvT_pts'] = S['xvT'].unsqueeze(1).expand(d, L, N).reshape(d, L * N).contiguous()
-        # start values and their x-gradient (the h -> y0 path of nabla_x u, src/model.py:95)
-        if tab is not None:                   # (tabulate_sample: evaluated once for all groups of the sample)
-            starts_T0 = bool(tab['starts_T0'])
-            S['start'] = _d64(tab['start'], dev).reshape(-1).contiguous()
-            S['ghT'] = _d64(tab['gh'], dev).t().contiguous()
-            S['h'] = _d64(tab['h'], dev).reshape(-1).contiguous()
-            S['f'] = _to_LN(tab['f'], dev)
-            w, gw = tab['w'], tab['gw']
-        elif N == 0:
-            # an empty share: the user's callables are not asked about no points (max(), indexing ... of an empty tensor)
-            starts_T0 = float(hints['t0'] if hints is not None else (shared_grid_t0 if shared_grid_t0 is not None else grids[0][0])) == self.setup['T0']
-            z = lambda *shape: torch.zeros(*shape, dtype=F64, device=dev)  # noqa: E731
-            S['start'], S['ghT'], S['h'], S['f'] = z(0), z(d, 0), z(0), z(L, 0)
-            Lw = 1 if getattr(domain, 'time_independent', False) else L
-            w, gw = z(0, Lw), z(0, Lw, d + 1)
-        else:
-            X0 = X[:, 0, :].clone().requires_grad_(True)
-            t_first = grids[0][0] if grids is not None else X[0, 0, 0]
-            starts_T0 = (float(t_first) if shared_grid_t0 is None else float(shared_grid_t0)) == self.setup['T0']
-            s = self.funcs['h'](X0) if starts_T0 else self.funcs['g'](X0.unsqueeze(1)).reshape(-1)
-            S['start'] = _d64(s.detach(), dev).reshape(-1).contiguous()
-            if s.requires_grad:
-                S['ghT'] = torch.autograd.grad(s.sum(), X0)[0][:, 1:].to(dev).to(F64).t().contiguous()
-            else:
-                S['ghT'] = torch.zeros(d, N, dtype=F64, device=dev)
-            # (a group that starts at T0: h(X[:, 0, :]) is the start value itself)
-            S['h'] = S['start'] if starts_T0 else self.funcs['h'](X[:, 0, :]).detach().to(dev).to(F64).reshape(-1).contiguous()
-            S['f'] = _to_LN(self.funcs['f'](X), dev)
-            # distance weight on the v-sample and its gradient (nabla phi = w nabla v + v nabla w, src/loss.py:51-63): in
-            # closed form where the domain offers it (identical to autograd's, ties included), on the first time slice only
-            # where w does not depend on time
-            XVw = XV[:, :1] if getattr(domain, 'time_independent', False) else XV
-            if hasattr(domain, 'func_w_grad'):
-                w, gw = domain.func_w_grad(XVw)
-            else:
-                XVl = XVw.clone().requires_grad_(True)
-                w = domain.func_w(XVl)
-                gw = torch.autograd.grad(w.sum(), XVl)[0] if w.requires_grad else torch.zeros_like(XVl)
-        if getattr(domain, 'time_independent', False):
-            S['w'] = _d64(w[:, 0].detach(), dev).contiguous()
-            S['wt'] = None
-        else:
-            S['w'] = _to_LN(w, dev)
-            S['wt'] = _to_LN(gw[:, :, 0], dev)
-        S['w0'] = _d64(w[:, 0].detach(), dev).contiguous()
-        S['gwx0T'] = _d64(gw[:, 0, 1:], dev).t().contiguous()
-        S['xbT'] = S['start_b'] = S['g'] = S['tb'] = None
-        Lb, same_grid, b_T0 = 0, True, False
-        if BX is not None:
-            Lb = BX.shape[1]
-            S['tb'] = _d64(grids[1] if grids is not None else BX[0, :, 0], dev).contiguous()
-            same_grid = Lb == L and (shared_grid_t0 is not None or (hints['same_grid'] if hints is not None else bool(torch.equal(S['tb'], S['t']))))
-            S['xbT'] = _d64(BX[:, 0, 1:], dev).t().contiguous()
-            if tab is not None:
-                b_T0 = bool(tab['b_T0'])
-                S['start_b'] = _d64(tab['start_b'], dev).reshape(-1).contiguous()
-                S['g'] = _to_LN(tab['g'], dev)
-            elif Nb == 0:
-                b_T0 = float(hints['tb0'] if hints is not None else (shared_grid_t0 if shared_grid_t0 is not None else grids[1][0])) == self.setup['T0']
-                S['start_b'], S['g'] = torch.zeros(0, dtype=F64, device=dev), torch.zeros(Lb, 0, dtype=F64, device=dev)
-            else:
-                tb_first = grids[1][0] if grids is not None else BX[0, 0, 0]
-                b_T0 = (float(tb_first) if shared_grid_t0 is None else float(shared_grid_t0)) == self.setup['T0']
-                sb = self.funcs['h'](BX[:, 0, :]) if b_T0 else self.funcs['g'](BX[:, 0, :].unsqueeze(1)).reshape(-1)
-                S['start_b'] = _d64(sb.detach(), dev).reshape(-1).contiguous()
-                S['g'] = _to_LN(self.funcs['g'](BX), dev)
-        st = self.structure
-        S['X'] = X.to(dev) if st.c_kappa is None else None      # only read by a general reaction callable c(u, t, x)
-        S['A0'] = S['B0'] = None
-        amode = 0
-        if not st.a_identity and N > 0:
-            S['A0'], amode = self._tabulate_a(X[:, :1, :])     # [d,d,N] / [d,N] (diagonal) / [d,d] (constant) at time index 0
-        if not st.b_zero and N > 0:
-            S['B0'] = self._tabulate_b(X[:, :1, :])            # [d, N]
-        if self.verify_structure and verify:
-            ver = getattr(into, 'sample_version', 0) if into is not None else 0
-            if ver % self.verify_every == 0 and N > 0:   # the first sample of a group and every verify_every-th refill after it
-                self._check_structure(X, ver // self.verify_every)
-        vol = float(domain.V())
-        nglob = float(n_glob if n_glob is not None else N)
-        nbglob = float(nb_glob if nb_glob is not None else max(Nb, 1))
-        # single-slice groups at T0: the reference's [N,N] broadcasts in factorised form.  The sums over m of the pair
-        # tables only involve the SAMPLE (h, f, g), so they are formed here, once per sample:
-        #   mean_nm (u_n - h_m)^2 = mean_n (u_n - mean h)^2 + var h          (src/loss.py:79; :84 likewise with g)
-        #   sum_mn f_m phi_n      = N sum_n mean(f) phi_n                    (src/loss.py:70)
-        pair_i = self.pairwise_single_slice and L == 1 and starts_T0
-        pair_b = self.pairwise_single_slice and (nb_glob if sharded else Nb) > 0 and Lb == 1 and b_T0
-        S['href'] = None
-        init_off = bdry_off = 0.0
-        if pair_i and not st.b_zero:
-            raise XnwanError('func_b != 0 on a single-slice group at T0: the reference sums that term with np.sum over a list of '
-                             'tensors (src/loss.py:69), whose result on its [N,N] broadcast depends on the numpy version -- not '
-                             'reproducible; set XW_ELEMENTWISE_SINGLE_SLICE=1 for the elementwise form')
-        if pair_i or pair_b:
-            zero = torch.zeros((), dtype=F64, device=dev)
-            gsum, gsq = (S['g'].sum(), (S['g'] ** 2).sum()) if pair_b else (zero, zero)
-            stats = torch.stack([S['h'].sum(), (S['h'] ** 2).sum(), S['f'].sum(), gsum, gsq]).contiguous()
-            if sharded:
-                self.world.all_reduce(stats)                 # the means are over ALL paths of the group, not this rank's share
-            sh, shh, sf, sg, sgg = stats.tolist()
-            if pair_i:
-                S['href'] = torch.full((N,), sh / nglob, dtype=F64, device=dev)
-                S['f'] = torch.full_like(S['f'], sf / nglob)
-                init_off = shh / nglob - (sh / nglob) ** 2
-            if pair_b:
-                S['g'] = torch.full_like(S['g'], sg / nbglob)
-                bdry_off = sgg / nbglob - (sg / nbglob) ** 2
-        # `sharded`: the sums of this group are partial sums (exchange steps in its sub-steps); `has_bdry`: the GROUP has boundary
-        # paths, whether or not this rank holds any (which parameters Adam skips must not depend on the rank, _gen_back)
-        pair_state = dict(pair_i=pair_i, pair_b=pair_b, init_off=init_off, bdry_off=bdry_off, s3_scale=nglob if pair_i else 1.0,
-                          sharded=sharded, has_bdry=BX is not None and (nb_glob if sharded else Nb) > 0)
-        if into is not None:
-            G = into
-            same = (G.N, G.L, G.Nb, G.Lb, G.same_grid, G.Vol, G.Nglob, G.Nbglob, G.pair_i, G.pair_b, G.amode, G.sharded) == (
-                N, L, Nb, Lb, same_grid, vol, nglob, nbglob, pair_i, pair_b, amode, sharded) and all(
-                (getattr(G, k) is None) == (S[k] is None) and (S[k] is None or getattr(G, k).shape == S[k].shape)
-                for k in Group.SAMPLE_FIELDS)
-            if same:
-                for k in Group.SAMPLE_FIELDS:
-                    if S[k] is not None:
-                        getattr(G, k).copy_(S[k])
-                G.domain = domain
-                G.__dict__.update(pair_state)
-                G.sample_version += 1
-                self._form_xproj(G)
-                return G
-        G = Group()
-        for k in Group.SAMPLE_FIELDS:
-            setattr(G, k, S[k])
-        G.domain, G.N, G.L, G.Nb, G.Vol, G.Nglob, G.Nbglob = domain, N, L, Nb, vol, nglob, nbglob
-        G.Lb, G.same_grid, G.amode = Lb, same_grid, amode
-        G.__dict__.update(pair_state)
-        # work buffers
-        # XW_POISON=1 (debugging): work buffers start as NaN instead of whatever the allocator hands out, so that a kernel
-        # reading a slot nobody wrote shows up as NaN in the results instead of as a stale, plausible number
-        self._work_buffers(G, [])
-        G.graphs = {}
-        # (a group of a list domain changes shape with every sample and is built anew each time: the count of samples it has seen
-        #  is carried over, or the periodic structure guard above -- two read-backs -- would run on EVERY sample)
-        G.sample_version = into.sample_version + 1 if into is not None else 0
-        self._form_xproj(G)
-        return G
-
-    def load_groups_packed(self, shards, hints, domain, cache, big):
-        """load_group for ALL groups of a list-domain sample at once (time-varying balls: 11-20 groups): every sample field of
-        every group is a strided view of the uploaded sample or of a table tabulate_sample has just filled for the whole
-        sample, so the fields are regions of each group's one allocation (Group._arena) and ONE gather launch
-        (kernels.gather_fields, a ~350-row table uploaded once) fills them -- instead of ~45 tensor operations per group.
-        Same values bit for bit (copies), same Group attributes.  Returns None when the sample is not of that kind (anything
-        but float64 device tensors, general a / b / c, no batched tabulation): the caller goes group by group.
-        `shards`: (X, XV, BX, n_glob, nb_glob, grids) per group as in load_group -- with several ranks this rank's shares (possibly
-        empty) of the groups that are sharded, the whole of those that are replicated."""
-        tc = getattr(self, '_tab_cat', None)
-        st = self.structure
-        if (tc is None or not (st.a_identity and st.b_zero and st.c_kappa is not None)
-                or getattr(domain, 'time_independent', False) or any(h is None for h in hints)):
-            return None
-        srcs = [tc[k] for k in ('f', 'g', 'w', 'gw', 'start', 'gh', 'h', 'start_b')]
-        if any(t.dtype != F64 or not t.is_cuda for t in srcs) or any(t.dtype != F64 or not t.is_cuda or t_[0] is not t_[1]
-                                                                       for t_ in shards for t in t_[:3]):
-            return None
-        d, dev, T0 = self.d, self.dev, self.setup['T0']
-        f_cat, g_cat, w_cat, gw_cat, start, gh, hv, sb = srcs
-        if f_cat.stride(0) != 1 or g_cat.stride(0) != 1 or w_cat.stride(0) != 1:
-            return None
-        g0, g1 = gw_cat.stride()
-        h0, h1 = gh.stride()
-        rows, groups, total = [], [], 0
-        oN = oNL = oNb = oNbL = 0
-        vol = float(domain.V())
-        for k, ((X, XV, BX, n_glob, nb_glob, grids), hn) in enumerate(zip(shards, hints)):
-            N, L, Nb, Lb = X.shape[0], X.shape[1], BX.shape[0], BX.shape[1]
-            sharded = n_glob is not None and self.world is not None
-            shared = bool(hn['shared_times'])
-            same_grid = Lb == L and bool(hn['same_grid'])
-            starts_T0, b_T0 = bool(tc['at0'][k]), bool(tc['bat0'][k])
-            G = Group()
-            G.domain, G.N, G.L, G.Nb, G.Vol = domain, N, L, Nb, vol
-            G.Nglob, G.Nbglob = float(n_glob if n_glob is not None else N), float(nb_glob if nb_glob is not None else max(Nb, 1))
-            G.Lb, G.same_grid, G.amode = Lb, same_grid, 0
-            fields = [('t', (L,)), ('xT', (d, N))]
-            if not shared:
-                fields += [('tpp', (L * N,)), ('tpp0', (N,)), ('xvT_pts', (d, L * N))]
-            fields += [('start', (N,)), ('ghT', (d, N)), ('h', (N,)), ('f', (L, N)), ('w', (L, N)), ('wt', (L, N)), ('w0', (N,)), ('gwx0T', (d, N)),
-                       ('tb', (Lb,)), ('xbT', (d, Nb)), ('start_b', (Nb,)), ('g', (Lb, Nb))]
-            self._work_buffers(G, fields, cached_table=False)
-            G._lazy['xvT'] = G._lazy['xT']           # (the v sample of a list domain is the u sample)
-            if shared:
-                G.tpp = G.tpp0 = G.xvT_pts = None
-            G.href = G.X = G.A0 = G.B0 = None
-            base = G._arena.data_ptr()
-            x0, x1, x2 = X.stride()
-            b0, b1, b2 = BX.stride()
-            xp, bp = X.data_ptr(), BX.data_ptr()
-            # (the grids are those of the WHOLE group's first paths: load_group)
-            t_src = (xp, x1) if grids is None else (grids[0].data_ptr(), grids[0].stride(0))
-            tb_src = (bp, b1) if grids is None else (grids[1].data_ptr(), grids[1].stride(0))
-            src = {'t': (t_src[0], 1, 1, L, 0, 0, t_src[1]), 'xT': (xp + 8 * x2, 1, d, N, 0, x2, x0),
-                   'tpp': (xp, 1, L, N, 0, x1, x0), 'tpp0': (xp, 1, 1, N, 0, 0, x0), 'xvT_pts': (xp + 8 * x2, d, L, N, x2, 0, x0),
-                   'start': (start.data_ptr() + 8 * oN * start.stride(0), 1, 1, N, 0, 0, start.stride(0)),
-                   'ghT': (gh.data_ptr() + 8 * oN * h0, 1, d, N, 0, h1, h0),
-                   'h': (hv.data_ptr() + 8 * oN * hv.stride(0), 1, 1, N, 0, 0, hv.stride(0)),
-                   'f': (f_cat.data_ptr() + 8 * oNL, 1, L, N, 0, 1, L),
-                   'w': (w_cat.data_ptr() + 8 * oNL, 1, L, N, 0, 1, L),
-                   'wt': (gw_cat.data_ptr() + 8 * oNL * g0, 1, L, N, 0, g0, L * g0),
-                   'w0': (w_cat.data_ptr() + 8 * oNL, 1, 1, N, 0, 0, L),
-                   'gwx0T': (gw_cat.data_ptr() + 8 * (oNL * g0 + g1), 1, d, N, 0, g1, L * g0),
-                   'tb': (tb_src[0], 1, 1, Lb, 0, 0, tb_src[1]), 'xbT': (bp + 8 * b2, 1, d, Nb, 0, b2, b0),
-                   'start_b': (sb.data_ptr() + 8 * oNb * sb.stride(0), 1, 1, Nb, 0, 0, sb.stride(0)),
-                   'g': (g_cat.data_ptr() + 8 * oNbL, 1, Lb, Nb, 0, 1, Lb)}
-            for name, shape in fields:
-                a, n0_, n1_, n2_, s0_, s1_, s2_ = src[name]
-                if n0_ * n1_ * n2_ == 0:        # (an empty share: nothing to gather)
-                    continue
-                rows.append((a, base + 8 * G._lazy[name][0], n0_, n1_, n2_, s0_, s1_, s2_, total))
-                total += n0_ * n1_ * n2_
-            has_bdry = (nb_glob if sharded else Nb) > 0
-            pair_i = self.pairwise_single_slice and L == 1 and starts_T0
-            pair_b = self.pairwise_single_slice and has_bdry and Lb == 1 and b_T0
-            G.__dict__.update(dict(pair_i=pair_i, pair_b=pair_b, init_off=0.0, bdry_off=0.0, s3_scale=G.Nglob if pair_i else 1.0,
-                                   sharded=sharded, has_bdry=has_bdry))
-            old = cache[k] if k < len(cache) else None
-            G.graphs = {}
-            ver = old.sample_version if old is not None else 0
-            G.sample_version = ver + 1 if old is not None else 0
-            if self.verify_structure and k == big and ver % self.verify_every == 0:      # (as load_group: the first sample and every 16th)
-                self._check_structure(X, ver // self.verify_every)
-            groups.append(G)
-            oN, oNL, oNb, oNbL = oN + N, oNL + N * L, oNb + Nb, oNbL + Nb * Lb
-        if len(rows) > KN.GATHER_ROWS:
-            return None
-        table = torch.zeros(KN.GATHER_ROWS, 9, dtype=torch.int64)
-        table[:len(rows)] = torch.tensor(rows, dtype=torch.int64)
-        from .sampling import _PIN_POOL
-        pinned = _PIN_POOL.stage(table)
-        tdev = pinned.to(dev, non_blocking=True)
-        _PIN_POOL.uploaded(pinned, torch.cuda.current_stream(dev))
-        KN.gather_fields(tdev, len(rows), total)
-        for G in groups:
-            self._form_xproj(G)
-        # single-slice groups at T0: the reference's [N, N] broadcasts in factorised form (load_group); these read five sums back
-        for G in groups:
-            if G.pair_i and not st.b_zero:
-                raise XnwanError('func_b != 0 on a single-slice group at T0 (see load_group)')
-            if G.pair_i or G.pair_b:
-                zero = torch.zeros((), dtype=F64, device=dev)
-                gsum, gsq = (G.g.sum(), (G.g ** 2).sum()) if G.pair_b else (zero, zero)
-                stats = torch.stack([G.h.sum(), (G.h ** 2).sum(), G.f.sum(), gsum, gsq]).contiguous()
-                if G.sharded:
-                    self.world.all_reduce(stats)             # (the means are over ALL paths of the group: load_group)
-                sh, shh, sf, sg, sgg = stats.tolist()
-                if G.pair_i:
-                    G.href = torch.full((G.N,), sh / G.Nglob, dtype=F64, device=dev)
-                    G.f.fill_(sf / G.Nglob)
-                    G.init_off = shh / G.Nglob - (sh / G.Nglob) ** 2
-                if G.pair_b:
-                    G.g.fill_(sg / G.Nbglob)
-                    G.bdry_off = sgg / G.Nbglob - (sg / G.Nbglob) ** 2
-        return groups
-
-    def _work_buffers(self, G, fields, cached_table=True):
-        """every buffer the sub-steps of G need, as regions of ONE allocation (Group._arena / _lazy), behind the regions `fields`
-        = [(name, shape)] the caller fills itself (load_groups_packed: the sample fields)"""
-        dev, d, N, L, Nb, Lb = self.dev, self.d, G.N, G.L, G.Nb, G.Lb
-        poison = self.options.poison
-        H = self.H
-        # stage activations of every step, written by the forward, read back by the sweeps (183 MB at N = 4096, L = 32)
-        ar = KN.ode_act_rows(self.method, H, self.K, self.m) if self.keep_activations and not self.adjoint else 0
-        # layer inputs of the test network at every point, stored by its forward in the discriminator sub-step and read
-        # back by its backward (524 MB at 131072 points)
-        # (only the reference's width and depth have a recomputing reverse kernel: everything else always runs from the record)
-        keep_v = self.keep_activations or self.testnet_tiled or not KN.disc_recompute(self.W, self.q)
-        G.ns_u = KN.ode_bwd_slabs(N)
-        G.ns_b = KN.ode_bwd_slabs(Nb) if Nb else 0
-        nw = KN.reduce_work_size()
-        plan = list(fields) + [('u', (L, N)), ('Y', (L, H, N)), ('v', (L, N)), ('vt', (L, N)), ('gxv', (d, N)), ('gtv', (N,)), ('gx', (d, N)), ('gs', (N,)),
-                ('vbar', (L, N)), ('s3x', (N,)),
-                ('slabA', (G.ns_u + G.ns_b, self.Pu)),         # sweep with cotangent A (interior) + the boundary sweep
-                ('slabB', (G.ns_u, self.Pu)),                  # sweep with cotangent B = dI/du
-                ('slab_v', (KN.disc_bwd_slabs(N, L), self.Pv)),
-                ('work_i', (nw,)), ('work_b', (nw,))]          # scratch of the deterministic grid sums (interior / boundary run concurrently): zeroed below
-        if ar:
-            plan.append(('act', (max(L - 1, 1), ar, KN.ode_act_cols(N))))
-            if Nb:
-                plan.append(('act_b', (max(Lb - 1, 1), ar, KN.ode_act_cols(Nb))))
-        if keep_v:
-            plan.append(('vact', (KN.disc_act_rows(self.W, self.q), KN.disc_act_cols(L * N))))
-        # (below xproj_min_d the table only pays without its head launch: path-mode groups, whose table is cached)
-        point_mode = G.__dict__.get('tpp') is not None or any(n_ == 'tpp' for n_, _ in fields)
-        if N and (d >= self.xproj_min_d or (cached_table and d >= self.xproj_table_min_d and not point_mode)):
-            plan.append(('xproj', (KN.disc_xproj_rows(self.W), N)))   # Vin[:, 1..d] x + Vin.b per path (_launch_test_net_here)
-        if Nb:
-            plan += [('ub', (Lb, Nb)), ('Yb', (Lb, H, Nb))]
-        lazy, off = {}, 0
-        for name, shape in plan:
-            lazy[name] = (off, shape)
-            off += -(-math.prod(shape) // 64) * 64           # (regions start on 512-byte boundaries, like allocations of their own)
-        G._arena = torch.full((off,), float('nan'), dtype=F64, device=dev) if poison else torch.empty(off, dtype=F64, device=dev)
-        G._lazy = lazy
-        w0 = lazy['work_i'][0]
-        G._arena[w0:lazy['work_b'][0] + nw].zero_()
-        G.c = G.cp = None
-        if not ar:
-            G.act = G.act_b = None
-        elif not Nb:
-            G.act_b = None
-        if not keep_v:
-            G.vact = None
-
-    def refill_compact(self, G, comp, domain, n_glob=None, nb_glob=None):
-        """load_group(..., into=G) for a COMPACT sample of a domain whose paths are vertical lines over one shared grid
-        (times [L], x_u [N, d], x_v [N, d], x_b [N_b, d]; host tensors, page-locked ones upload asynchronously): the
-        sample goes into four static device buffers and everything load_group does with it on the device -- the path
-        tensors, the callables h (with its gradient), f, g, the domain's weight, the transposes and conversions into the
-        group's sample fields, ~110 small kernels -- is captured ONCE per shape into a HIP graph and replayed: an outer
-        iteration of train() at the headline size spent 1.0 of its 2.4 ms of host time issuing them one by one.  Same
-        rule as the sub-step graphs (_run): a callable that cannot be captured (it syncs with the host) makes this
-        segment eager, with a warning.  The guard on the probed coefficient structure stays outside the graph."""
-        times = comp[0]
-        st = G.__dict__.get('_refill_in')
-        if st is None or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(st, comp)):
-            st = G._refill_in = [torch.empty(tuple(c.shape), dtype=c.dtype, device=self.dev) for c in comp]
-            G.graphs = {k: v for k, v in G.graphs.items() if not k.startswith('refill')}
-        for dst, src in zip(st, comp):
-            dst.copy_(src, non_blocking=True)
-        _PIN_POOL.uploaded_all(comp, torch.cuda.current_stream(self.dev))
-        t0 = float(times[0])                                   # (host tensor: no device read-back)
-        td, du, dv, db = st
-        ver = G.sample_version
-        if self.verify_structure and ver % self.verify_every == 0:
-            self._check_structure(_paths(td, du), ver // self.verify_every)
-
-        lean = (self.structure.a_identity and self.structure.b_zero and self.structure.c_kappa is not None
-                and getattr(domain, 'time_independent', False) and hasattr(domain, 'func_w_grad') and G.Nb > 0 and G.same_grid
-                and not (G.pair_i or G.pair_b) and G.tpp is None
-                and (G.N, G.L, G.Nb, G.Lb) == (du.shape[0], td.shape[0], db.shape[0], td.shape[0])
-                and float(domain.V()) == G.Vol and n_glob in (None, G.Nglob) and nb_glob in (None, G.Nbglob))
-
-        def body(_G):
-            if lean:
-                self._refill_fields(G, td, du, dv, db, domain, t0)
-                self._form_xproj(G)      # (the new sample's table, part of the refill graph: outside every sub-step)
-                return
-            out = self.load_group(_paths(td, du), _paths(td, dv), _paths(td, db), domain, n_glob, nb_glob, into=G, shared_grid_t0=t0,
-                                  verify=False)
-            if out is not G:
-                raise XnwanError('refill_compact: the sample does not have the shapes of the group it refills')
-        # (what the captured body bakes in besides the buffers: the grid's first time, the domain's class and extent, which of
-        #  the two bodies it is and the global path counts)
-        key = 'refill_%r_%s_%r_%r_%r_%d_%r_%r' % (t0, type(domain).__name__, float(domain.V()), getattr(domain, 'top', None),
-                                                  getattr(domain, 'bot', None), int(lean), n_glob, nb_glob)
-        if key not in G.graphs and sum(1 for k in G.graphs if k.startswith('refill')) >= self.refill_variants:
-            # a domain whose first time or extent changes with every sample would capture a graph per outer iteration (graphs are
-            # never destroyed, _KEPT_GRAPHS): beyond a few variants per group the refill runs eagerly
-            if not G.__dict__.get('_refill_cap_warned'):
-                import warnings
-                G._refill_cap_warned = True
-                warnings.warn('more than %d variants of the refill graph for one group (first time / extent / path counts change from '
-                              'sample to sample): further variants run as eager launches' % self.refill_variants, RuntimeWarning, stacklevel=2)
-            G.graphs[key] = False
-        self._run(G, key, body, scratch=True)
-        # (host-side bookkeeping of load_group: done at capture time only, so it is set here on every path)
-        G.domain, G.sample_version = domain, ver + 1
-        if self._xproj_held(G):
-            G.xproj_key = self._v_key(G)
-        return G
-
-    def _refill_fields(self, G, td, du, dv, db, domain, t0):
-        """What load_group(paths(td, du), paths(td, dv), paths(td, db), into=G, shared_grid_t0=t0) writes into the sample
-        fields of a group of vertical paths over ONE grid, on a time-independent domain with the fused coefficient structure
-        (a = identity, b = 0, c = kappa u) -- the same values bit for bit (the same callables on the same tensors; every
-        conversion is an exact float32 -> float64 widening or a transpose), written straight into the fields: a widening, a
-        transpose and the copy into the field are ONE strided copy here and three kernels there (~110 -> ~85 per sample).
-        The four independent chains -- f on the interior paths | the start values h with their gradient | the domain's
-        weight | the boundary paths -- run on the engine's side streams: captured (refill_compact), that makes them
-        parallel branches of the graph, and the GPU has nothing else to do between two outer iterations."""
-        T0, fn = self.setup['T0'], self.funcs
-        at0 = float(t0) == T0
-        e0 = self._mark()
-        with self._side(1, e0):                       # start values and their x-gradient (the h -> y0 path of nabla_x u)
-            X0 = _paths(td[:1], du)[:, 0, :].requires_grad_(True)
-            s_ = fn['h'](X0) if at0 else fn['g'](X0.unsqueeze(1)).reshape(-1)
-            G.start.copy_(s_.detach().reshape(-1))
-            if s_.requires_grad:
-                G.ghT.copy_(torch.autograd.grad(s_.sum(), X0)[0][:, 1:].t())
-            else:
-                G.ghT.zero_()
-            # (a group that starts at T0: h on its first points IS the start value)
-            G.h.copy_(G.start if at0 else fn['h'](X0.detach()).reshape(-1))
-            e1 = self._mark()
-        with self._side(2, e0):                       # distance weight on the v-sample, first time slice (time-independent)
-            stock = type(domain).func_w_grad is Hypercube.func_w_grad and type(domain).func_w is Hypercube.func_w
-            if stock and dv.dtype == F32 and dv.is_contiguous():
-                # the stock hypercube: its weight, the gradient and the transposed points in ONE launch (xw_cube_weight: same
-                # float32 arithmetic, same tie rules as the tensor formulation below, which takes 29)
-                KN.cube_weight(dv, domain.top, domain.bot, G.w, G.gwx0T, w0=G.w0, xT=G.xvT)
-            else:
-                w, gw = domain.func_w_grad(_paths(td[:1], dv))
-                G.w.copy_(w[:, 0].detach())
-                G.w0.copy_(w[:, 0].detach())
-                G.gwx0T.copy_(gw[:, 0, 1:].t())
-                G.xvT.copy_(dv.t())
-            e2 = self._mark()
-        with self._side(3, e0):                       # boundary paths
-            BX = _paths(td, db)
-            sb = fn['h'](BX[:, 0, :]) if at0 else fn['g'](BX[:, 0, :].unsqueeze(1)).reshape(-1)
-            G.start_b.copy_(sb.detach().reshape(-1))
-            G.g.copy_(fn['g'](BX).detach().t())
-            G.xbT.copy_(db.t())
-            G.tb.copy_(td)
-            e3 = self._mark()
-        G.t.copy_(td)
-        G.xT.copy_(du.t())
-        G.f.copy_(fn['f'](_paths(td, du)).detach().t())
-        self._join(e1, e2, e3)
 
     # ------------------------------------------------------------------------------------------------------------
     # building blocks
@@ -1831,8 +1106,7 @@ class Engine:
     def predict(self, X):
         """u_theta on a group [N, L, d+1] -> [L, N] (diagnostics; no checkpoints kept)"""
         Xd = X.detach()
-        starts_T0 = float(Xd[0, 0, 0]) == self.setup['T0']
-        s = self.funcs['h'](Xd[:, 0, :]) if starts_T0 else self.funcs['g'](Xd[:, 0, :].unsqueeze(1)).reshape(-1)
+        s = start_values(self.funcs, Xd[:, 0, :], at_T0(self.setup['T0'], first=Xd[0, 0, 0]), False)
         return self._u_forward(Xd[:, 0, 1:].to(self.dev).to(F64).t().contiguous(), Xd[0, :, 0].to(self.dev).to(F64).contiguous(),
                                s.detach().to(self.dev).to(F64).reshape(-1).contiguous())
 

@@ -25,6 +25,7 @@ from . import nets, sampling
 from .sampling import HIP_HOST_LOCK
 from ._lib import XnwanError
 from .engine import Engine
+from .groups import at_T0, batched_start_values
 from .options import EngineOptions
 from .kernels import adam as _adam_kernel
 
@@ -458,21 +459,13 @@ class NODE_WAN_solver:
             return None
         Xs, hints = packed
         d1, T0 = self.setup['dim'] + 1, self.setup['T0']
-        at0 = [h['t0'] == T0 for h in hints]
+        at0 = [at_T0(T0, hint=h['t0']) for h in hints]
         with torch.no_grad():
             sol = self.func_u_sol(torch.cat([x.reshape(-1, 1, d1) for x in Xs], 0)).reshape(-1)
             sols = iter([s_.view(x.shape[0], x.shape[1]) for s_, x in zip(sol.split([x.shape[0] * x.shape[1] for x in Xs]), Xs)])
             # start values: h on the first points of the groups that start at T0, g on those that start on the moving boundary
-            P0 = torch.cat([x[:, 0, :] for x in Xs], 0)
-            n = [x.shape[0] for x in Xs]
-            # (groups are contiguous row ranges of P0: slices, not an index tensor -- see Engine.tabulate_sample)
-            rows = P0.split(n)
-            rows_h, rows_g = [r for r, a in zip(rows, at0) if a], [r for r, a in zip(rows, at0) if not a]
-            hval = self.func_h(torch.cat(rows_h, 0)).reshape(-1).double() if rows_h else None
-            gval = self.func_g(torch.cat(rows_g, 0).unsqueeze(1)).reshape(-1).double() if rows_g else None
-            it_h = iter(hval.split([r.shape[0] for r in rows_h])) if hval is not None else None
-            it_g = iter(gval.split([r.shape[0] for r in rows_g])) if gval is not None else None
-            start = torch.cat([next(it_h) if a else next(it_g) for a in at0], 0)
+            _, n, start = batched_start_values(lambda p: self.func_h(p).double(), lambda p: self.func_g(p).double(),
+                                               [x[:, 0, :] for x in Xs], at0)
             starts = iter(zip(start.split(n), at0))
             net.blob.check_alias()
 
