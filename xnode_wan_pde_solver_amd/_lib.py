@@ -44,6 +44,15 @@ class XwPathsGradJob(ctypes.Structure):   # include/xnwan_grad.h: one ragged gro
                 ('N', c_int)]
 
 
+class XwPathsDopriCkptJob(ctypes.Structure):   # include/xnwan_eval_grad.h: XwPathsDopriJob with the checkpoints kept (f.cap slots)
+    _fields_ = [('f', XwPathsDopriJob), ('ckpt', c_vp)]
+
+
+class XwPathsDopriGradJob(ctypes.Structure):   # include/xnwan_eval_grad.h: one group of xw_paths_dopri5_grad (the sweep behind it)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('t_in', c_vp), ('t_end', c_vp), ('n_acc', c_vp), ('rec', c_vp), ('ckpt', c_vp),
+                ('Y', c_vp), ('gx', c_vp), ('gs', c_vp), ('ut', c_vp), ('N', c_int), ('cap', c_int)]
+
+
 class XwDopriJob(ctypes.Structure):       # include/xnwan.h: solver 'dopri5', one job of the forward launches
     _fields_ = [('xT', c_vp), ('start', c_vp), ('u', c_vp), ('Y', c_vp), ('rec_y', c_vp), ('rec_t', c_vp), ('rec_h', c_vp),
                 ('fbuf', c_vp), ('ctl', c_vp), ('work', c_vp), ('N', c_int), ('cap', c_int)]
@@ -178,7 +187,16 @@ GRAD_SIGNATURES = {
 }
 
 
-class XwSwitches(ctypes.Structure):       # include/xnwan_switches.h: the library's process-wide switches
+# the extension header include/xnwan_eval_grad.h: same conventions
+EVAL_GRAD_SIGNATURES = {
+    'xw_paths_dopri5_ckpt_fwd': [ctypes.POINTER(XwPathsDopriCkptJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl,
+                                 c_int, c_int, c_f64p, c_vp],
+    'xw_paths_dopri5_grad_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_dopri5_grad': [ctypes.POINTER(XwPathsDopriGradJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_f64p, c_vp],
+}
+
+
+class XwSwitches(ctypes.Structure):      # include/xnwan_switches.h: the library's process-wide switches
     _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
 
 
@@ -209,7 +227,7 @@ def _load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(GRAD_SIGNATURES.items())
-                           + list(SWITCH_SIGNATURES.items())):
+                           + list(EVAL_GRAD_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

@@ -18,8 +18,12 @@
 // the job copy the last path and store nothing.  A tile's loop ends when all its paths are done, or after max_attempts rounds: a
 // path still open then gets XW_DOPRI_STEPS.  No float atomics, no tickets, no waits between tiles: a path's bits do not depend on its
 // tile neighbours, and the launch can be captured.  The workspace is the tiled dopri5 forward's, td_work(0, ...).
+//
+// ckpt (include/xnwan_eval_grad.h: xw_paths_dopri5_ckpt_fwd; null from xw_paths_dopri5_fwd) keeps, per path, the state at the start
+// of every accepted step below the job's cap -- what kq_paths_grad (xw_tdopri_paths_grad.hip) walks back.  Stores only: with or
+// without it every other output is the same bits.
 #include "xw_common.h"
-#include "xnwan_eval.h"
+#include "xnwan_eval_grad.h"
 
 namespace {
 #include "xw_generic_cot.h"   // (not used by this forward pass: the sweep helpers of xw_tiled_blocks.h name cot_u / cot_job_ok)
@@ -32,7 +36,7 @@ __device__ __forceinline__ double gsum64(double x) { return xw_sum_over_g(xw_sum
 
 __global__ void __launch_bounds__(64) kq_paths(const XwPathsDopriJob job, const double* __restrict__ theta, int d, int H, int K, int m,
                                                int Hn, double rtol, double atol, int max_steps, int max_attempts,
-                                               double* __restrict__ work) {
+                                               double* __restrict__ work, double* __restrict__ ckpt) {
   const int N = job.N, p0 = blockIdx.x * 16;
   const Net n = {theta, u_offsets(d, H, K), d, H, K, m};
   const TdWork q = td_work(0, d, H, K, m);
@@ -46,10 +50,12 @@ __global__ void __launch_bounds__(64) kq_paths(const XwPathsDopriJob job, const 
   const int l16 = lane_id() & 15;
   const int pc = p0 + l16 < N ? p0 + l16 : N - 1;            // the lane's own path
   const bool mine = lane_id() < 16 && p0 + l16 < N;          // ... and the lane that stores its scalars
+  const bool keep = ckpt != nullptr && p0 + l16 < N;         // the lane stores its column's checkpoints
   const double t_end = job.t_end[pc], cnt = (double)Hn;
   if (lane_id() < 16) st[l16] = job.start[pc];
   tile_x(n, q.w, ws, job.xT, N, p0);
   tlift(n, st, pre, yf, y0);
+  if (ckpt) tstore(H, N, p0, y0, ckpt);                      // slot 0: the lifted start value, of every path
   // ---- the controller, per lane: ctl_init1 / ctl_init2 with N = 1 --------------------------------------------------------------
   double t0 = job.t_in[pc];
   tfield(n, q.w, ws, t0, y0, kk, false);
@@ -118,6 +124,7 @@ __global__ void __launch_bounds__(64) kq_paths(const XwPathsDopriJob job, const 
         yf[e] = y0[e] + s_;
       }
       if (accept) {                                          // commit: the candidate, and its last stage as the next k_0
+        if (keep && nacc >= 1 && nacc < job.cap) ckpt[((long)nacc * H + (e >> 4)) * N + pc] = y0[e];   // slot nacc: this step's start
         y0[e] = yt[e];
         kk[e] = kk[16L * H * 6 + e];
       }
@@ -165,23 +172,44 @@ extern "C" int xw_paths_dopri5_work(int d, int H, int K, int m) {
   return (int)td_work(0, d, H, K, m).total;
 }
 
-extern "C" int xw_paths_dopri5_fwd(const XwPathsDopriJob* jobs, int njobs, const double* theta, int d, int H, int K, int m, int Hn,
-                                   double rtol, double atol, int max_steps, int max_attempts, double* work, void* stream) {
+namespace {
+// the checks and launches of both entry points: job i as the kernel takes it is fwd(jobs[i]) with the checkpoints ckpt(jobs[i])
+template <class J, class F, class C>
+int paths_fwd(const J* jobs, int njobs, F fwd, C ckpt, const double* theta, int d, int H, int K, int m, int Hn, double rtol,
+              double atol, int max_steps, int max_attempts, double* work, void* stream) {
   if (!jobs || njobs < 1 || !theta || !work || !(rtol >= 0.0) || !(atol >= 0.0) || max_steps < 1 || max_attempts < 1) return XW_E_ARG;
   if (!xw_tiled_ode_ok(d, H, K, m)) return XW_E_DIMS;
   if (Hn < 1 || Hn > H) return XW_E_ARG;
   for (int i = 0; i < njobs; ++i) {
-    const XwPathsDopriJob& j = jobs[i];
-    if (!j.xT || !j.start || !j.t_in || !j.t_end || !j.u || !j.status || !j.n_acc || !j.n_att || j.N < 1 || (j.rec && j.cap < 0))
+    const XwPathsDopriJob& j = fwd(jobs[i]);
+    if (!j.xT || !j.start || !j.t_in || !j.t_end || !j.u || !j.status || !j.n_acc || !j.n_att || j.N < 1 || (j.rec && j.cap < 0) ||
+        (ckpt(jobs[i]) && j.cap < 1))
       return XW_E_ARG;
   }
   const long per = td_work(0, d, H, K, m).total;
   long off = 0;
   for (int i = 0; i < njobs; ++i) {
-    const int tiles = (jobs[i].N + 15) / 16;
-    hipLaunchKernelGGL(kq_paths, dim3(tiles), dim3(64), 0, (hipStream_t)stream, jobs[i], theta, d, H, K, m, Hn, rtol, atol, max_steps,
-                       max_attempts, work + off);
+    const int tiles = (fwd(jobs[i]).N + 15) / 16;
+    hipLaunchKernelGGL(kq_paths, dim3(tiles), dim3(64), 0, (hipStream_t)stream, fwd(jobs[i]), theta, d, H, K, m, Hn, rtol, atol,
+                       max_steps, max_attempts, work + off, ckpt(jobs[i]));
     off += per * tiles;
   }
   return xw_launch_status();
+}
+}  // namespace
+
+extern "C" int xw_paths_dopri5_fwd(const XwPathsDopriJob* jobs, int njobs, const double* theta, int d, int H, int K, int m, int Hn,
+                                   double rtol, double atol, int max_steps, int max_attempts, double* work, void* stream) {
+  return paths_fwd(jobs, njobs, [](const XwPathsDopriJob& j) -> const XwPathsDopriJob& { return j; },
+                   [](const XwPathsDopriJob&) -> double* { return nullptr; }, theta, d, H, K, m, Hn, rtol, atol, max_steps,
+                   max_attempts, work, stream);
+}
+
+// ... and include/xnwan_eval_grad.h: the same launches with the checkpoints kept
+extern "C" int xw_paths_dopri5_ckpt_fwd(const XwPathsDopriCkptJob* jobs, int njobs, const double* theta, int d, int H, int K, int m,
+                                        int Hn, double rtol, double atol, int max_steps, int max_attempts, double* work,
+                                        void* stream) {
+  return paths_fwd(jobs, njobs, [](const XwPathsDopriCkptJob& j) -> const XwPathsDopriJob& { return j.f; },
+                   [](const XwPathsDopriCkptJob& j) -> double* { return j.ckpt; }, theta, d, H, K, m, Hn, rtol, atol, max_steps,
+                   max_attempts, work, stream);
 }

@@ -15,7 +15,10 @@ chunk; evaluate_points takes it with tol = (rtol, atol).
 
 Gradients come from evaluate_points_grad alone (behind XNODE.evaluate_grad / NODE_WAN_solver.evaluate_grad): the fixed-grid forward
 with its checkpoints kept, then kernels.tiled_paths_grad (csrc/xw_tiled_paths_grad.hip), the reverse sweep over the same ragged
-group, and the chain rule through the start value (start_gradient).  Its docstring says what its `ut` is and what it refuses."""
+group, and the chain rule through the start value (start_gradient).  Its docstring says what its `ut` is and what it refuses.
+With solver 'dopri5' (tol given) it is three passes: paths_dopri5 for u and every path's step count, then, sorted by that count and
+cut by dopri5_grad_chunks, the same forward with its record and checkpoints kept and kernels.paths_dopri5_grad
+(csrc/xw_tdopri_paths_grad.hip), the reverse sweep over every path's own accepted steps (dopri5_grad_pass)."""
 import torch
 
 from . import kernels as KN
@@ -24,7 +27,7 @@ from ._lib import XnwanError
 F64 = torch.float64
 EVAL_CHUNK_PATHS = 65536                   # EngineOptions.eval_chunk_paths
 REFUSED_SOLVERS = ('dopri5', 'explicit_adams')
-EVAL_GRAD_CKPT_BYTES = 1 << 30             # evaluate_points_grad: the checkpoints Y [L, H, n] of one chunk stay below this
+EVAL_GRAD_CKPT_BYTES = 1 << 30             # evaluate_points_grad: a chunk's checkpoints (Y [L, H, n]; dopri5: ckpt [cap, H, n]) stay below this
 
 
 def step_counts(t, t_in, T0, T, n_sub):
@@ -102,6 +105,19 @@ def paths_dopri5(xT, t_in, t_end, start, theta, H, K, m, Hn, rtol, atol, max_ste
     return dict(u=u, fin=fin, status=words[0], n_acc=words[1], n_att=words[2])
 
 
+def raise_unreached(who, r, order, inverse, t, t_in, max_steps):
+    """XnwanError for the paths of r = paths_dopri5(...) (sorted by `order`) whose controller ended with a status: their count and
+    the first such point as the caller numbers them, with dopri5_status_message's words; nothing where every status is 0"""
+    bad = (r['status'] != 0).nonzero().view(-1)
+    if bad.numel():
+        i = int(order[bad.to(order.device)].min())
+        k = int(inverse[i])
+        fin = r['fin'][:, k].tolist()
+        msg = KN.dopri5_status_message(int(r['status'][k]), [fin[0], fin[1], int(r['n_acc'][k]), int(r['n_att'][k])], max_steps)
+        raise XnwanError('%s: %d of %d points did not reach their time (first: point %d, t = %r, t_in = %r): %s'
+                         % (who, bad.numel(), t.numel(), i, float(t[i]), float(t_in[i]), msg))
+
+
 def start_gradient(h, first):
     """dh/dx [M, d] at first = [t_in, x] ([M, 1 + d]): torch.autograd.grad of h(first).sum() with respect to a leaf copy of
     `first`, the time column dropped.  h is taken to act POINT BY POINT -- row i of its output depends on row i of its input alone,
@@ -124,7 +140,61 @@ def grad_chunk_paths(chunk, L, H):
     return min(chunk, max(16, 16 * (EVAL_GRAD_CKPT_BYTES // (8 * L * H * 16))))
 
 
-def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+def dopri5_grad_chunks(n_acc_sorted, H, chunk, budget=EVAL_GRAD_CKPT_BYTES):
+    """[(lo, hi, cap)]: the launches of dopri5_grad_pass over paths sorted by their accepted step count n_acc_sorted (a sequence of
+    ints).  cap = max(1, the largest count of the chunk), the slots of its record; hi - lo <= chunk; chunks are whole 16-path tiles
+    (the last one, or a chunk below 16, apart); and the checkpoints 8 cap H (hi - lo) bytes stay within `budget` wherever a chunk
+    holds more than one tile -- a memory bound, not a tuned number.  Every path is in exactly one chunk."""
+    n = [int(v) for v in n_acc_sorted]
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    limit = chunk - chunk % 16 if chunk >= 16 else chunk
+    out, lo = [], 0
+    while lo < len(n):
+        hi, cap = lo, 1
+        while hi < len(n) and hi - lo < limit:
+            nxt = min(hi + 16, len(n), lo + limit)
+            grown = max(cap, max(n[hi:nxt]))
+            if hi > lo and 8 * grown * H * (nxt - lo) > budget:
+                break
+            hi, cap = nxt, grown
+        out.append((lo, hi, cap))
+        lo = hi
+    return out
+
+
+def dopri5_grad_pass(xT, t_in, t_end, start, n_acc, theta, H, K, m, Hn, rtol, atol, max_steps=KN.DOPRI5_MAX_STEPS,
+                     chunk=EVAL_CHUNK_PATHS):
+    """the second forward and the sweep of evaluate_points_grad with solver 'dopri5', on N paths whose controllers have ended with
+    status 0 after n_acc [N] (host, int) accepted steps: the paths are sorted by that count (stable), so that the 16 paths of a tile
+    walk about the same rounds back, cut by dopri5_grad_chunks, and per chunk kernels.paths_dopri5_fwd runs again with rec, ckpt
+    and Y of exactly the chunk's largest count, then kernels.paths_dopri5_grad.  -> dict(u [N], gx [d, N], gs [N], ut [N]) on the
+    device, in the caller's order; u: the second forward's, the bits of the first (a path's bits depend on neither order nor
+    neighbours).  Nothing is read back."""
+    (d, N), dev = xT.shape, xT.device
+    order, inverse = sort_by_steps(torch.as_tensor(n_acc, dtype=torch.int64).cpu())
+    od = order.to(dev)
+    xs, ts, te, ss = xT[:, od].contiguous(), t_in[od].contiguous(), t_end[od].contiguous(), start[od].contiguous()
+    u = torch.empty(N, dtype=F64, device=dev)
+    gx = torch.empty(d, N, dtype=F64, device=dev)
+    gs, ut = torch.empty(N, dtype=F64, device=dev), torch.empty(N, dtype=F64, device=dev)
+    for lo, hi, cap in dopri5_grad_chunks(torch.as_tensor(n_acc)[order].tolist(), H, chunk):
+        k, whole = hi - lo, hi - lo == N
+        words = torch.empty(3, k, dtype=torch.int32, device=dev)
+        job = dict(xT=xs if whole else xs[:, lo:hi].contiguous(), start=ss[lo:hi], t_in=ts[lo:hi], t_end=te[lo:hi], u=u[lo:hi],
+                   status=words[0], n_acc=words[1], n_att=words[2], Y=torch.empty(H, k, dtype=F64, device=dev),
+                   rec=torch.empty(cap, 2, k, dtype=F64, device=dev), ckpt=torch.empty(cap, H, k, dtype=F64, device=dev))
+        KN.paths_dopri5_fwd([job], theta, H, K, m, Hn, rtol=rtol, atol=atol, max_steps=max_steps)
+        out = dict(gx=gx if whole else torch.empty(d, k, dtype=F64, device=dev), gs=gs[lo:hi], ut=ut[lo:hi])
+        KN.paths_dopri5_grad([dict(job, **out)], theta, H, K, m)
+        if not whole:
+            gx[:, lo:hi] = out['gx']
+    inv = inverse.to(dev)
+    return dict(u=u[inv], gx=gx[:, inv], gs=gs[inv], ut=ut[inv])
+
+
+def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS, tol=None,
+                         Hn=None, max_steps=KN.DOPRI5_MAX_STEPS):
     """u_theta, its gradient in x and its time derivative at points [M, 1 + d] (time first; host or device, float32 or float64)
     -> dict(u [M], grad [M, d], ut [M]), float64 on `device`.  Entry rule, step counts, packing and sort are evaluate_points';
     per chunk kernels.tiled_paths_fwd keeps the checkpoints and kernels.tiled_paths_grad walks them back:
@@ -133,13 +203,23 @@ def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method,
             through the start value h([T0, x]))
       ut    FL_w . F(t, x, y(t)): the time derivative of the CONTINUOUS model y' = F, u = FL y at fixed x -- not the derivative
             of the discrete u with respect to the end time of its grid (that would need the derivative of the steps in dt).
-    Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, and every point that is not
-    entered at T0 -- the hourglass's re-entered points, whose entry time |x| / r depends on x: holding it fixed would not give the
-    gradient.  No collective calls, no random numbers."""
-    if solver in REFUSED_SOLVERS:
+    tol = (rtol, atol) with solver 'dopri5' (Hn, max_steps: as evaluate_points takes them; n_sub must be None): every point is one
+    adaptive solve of its own, and the chain is three passes -- paths_dopri5 as evaluate_points runs it, for u (the bits of
+    evaluate_points), the status words and every path's count of accepted steps; then dopri5_grad_pass: the same forward again,
+    sorted by that count, with a record and checkpoints of exactly the size it needs, and the reverse sweep over them.  grad is
+    then du/dx of the discrete solution with every point's ACCEPTED STEPS held fixed (step sizes as constants, the last step
+    through its dense output at t: training's convention); ut as above, at the forward's y(t).
+    Refused: the solver 'explicit_adams', 'dopri5' without tol, a domain class without `entry`, t < t_in, and every point that is
+    not entered at T0 -- the hourglass's re-entered points, whose entry time |x| / r depends on x: holding it fixed would not give
+    the gradient.  No collective calls, no random numbers."""
+    adaptive = solver == 'dopri5' and tol is not None
+    if solver in REFUSED_SOLVERS and not adaptive:
         raise XnwanError("evaluate_grad(): solver %r is not served -- the reverse sweep over per-path time grids runs the fixed-grid "
                          "schemes %s only (it reverses the steps taken; no per-path step controller or multistep history is built)"
                          % (solver, sorted(KN.METHODS)))
+    if adaptive and n_sub is not None:
+        raise XnwanError("evaluate_grad(): n_sub = %r with solver 'dopri5' -- every point's step sizes are its controller's (rtol, "
+                         "atol); a number of steps over [T0, T] has no meaning there" % (n_sub,))
     entry = getattr(domain, 'entry', None)
     if entry is None:
         name = getattr(domain, '__name__', type(domain).__name__)
@@ -147,7 +227,7 @@ def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method,
                          'starts, and with which start value, is the domain\'s to say' % name)
     d, T0, T = setup['dim'], setup['T0'], setup['T']
     n_sub = setup['N_t'] if n_sub is None else n_sub
-    if n_sub < 1:
+    if not adaptive and n_sub < 1:
         raise XnwanError('evaluate_grad(): n_sub = %r, at least one step over [T0, T]' % (n_sub,))
     if chunk < 1:
         raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
@@ -175,6 +255,17 @@ def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method,
         first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
         s = h(first).reshape(-1).double()
         hx = start_gradient(h, first).to(F64)
+        if adaptive:
+            Hn, rtol, atol = H if Hn is None else Hn, float(tol[0]), float(tol[1])
+            order, inverse = sort_by_steps(t - t_in)         # (evaluate_points' sort: by the length of the interval)
+            xT, ts = pts[order, 1:].t().contiguous().to(device), t_in[order].contiguous().to(device)
+            te, start = t[order].contiguous().to(device), s[order].contiguous().to(device)
+            r = paths_dopri5(xT, ts, te, start, theta, H, K, m, Hn, rtol, atol, max_steps=max_steps, chunk=chunk)
+            raise_unreached('evaluate_grad()', r, order, inverse, t, t_in, max_steps)
+            g = dopri5_grad_pass(xT, ts, te, start, r['n_acc'], theta, H, K, m, Hn, rtol, atol, max_steps=max_steps, chunk=chunk)
+            inv = inverse.to(device)
+            grad = g['gx'].t()[inv] + g['gs'][inv].view(-1, 1) * hx.to(device)
+            return dict(u=r['u'][inv], grad=grad.contiguous(), ut=g['ut'][inv])
         n = step_counts(t, t_in, T0, T, n_sub)
         order, inverse = sort_by_steps(n)
         tT = pack_grids(t[order], t_in[order], n[order]).to(device)
@@ -250,14 +341,7 @@ def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H
             r = paths_dopri5(pts[order, 1:].t().contiguous().to(device), t_in[order].contiguous().to(device),
                              t[order].contiguous().to(device), s[order].contiguous().to(device), theta, H, K, m,
                              H if Hn is None else Hn, float(tol[0]), float(tol[1]), max_steps=max_steps, chunk=chunk)
-            bad = (r['status'] != 0).nonzero().view(-1)
-            if bad.numel():
-                i = int(order[bad.to(order.device)].min())       # the first such point, as the caller numbers them
-                k = int(inverse[i])
-                fin = r['fin'][:, k].tolist()
-                msg = KN.dopri5_status_message(int(r['status'][k]), [fin[0], fin[1], int(r['n_acc'][k]), int(r['n_att'][k])], max_steps)
-                raise XnwanError('evaluate(): %d of %d points did not reach their time (first: point %d, t = %r, t_in = %r): %s'
-                                 % (bad.numel(), t.numel(), i, float(t[i]), float(t_in[i]), msg))
+            raise_unreached('evaluate()', r, order, inverse, t, t_in, max_steps)
             return r['u'][inverse.to(device)]
         n = step_counts(t, t_in, T0, T, n_sub)
         order, inverse = sort_by_steps(n)

@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwPathsGradJob, XwSwitches)
+                   XwPathsGradJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -751,10 +751,12 @@ def paths_dopri5_fwd(jobs, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATO
     """solver 'dopri5' with a step controller PER PATH (csrc/xw_tdopri_paths.hip, include/xnwan_eval.h): every path is one odeint
     call of the reference on the one-path group with the sample times [t_in, t_end], the whole integration of a 16-path tile in one
     launch.  job = dict(xT[d,N], start[N], t_in[N], t_end[N] >= t_in, u[N], status[N], n_acc[N], n_att[N] (int32), optional Y[H,N]
-    -- the state at t_end --, rec[cap,2,N] -- t0 and dt of each accepted step below cap -- and fin[2,N] -- t0 and dt of every
-    controller when it stopped); theta at the widths (H, K), the generic layout; Hn: the network's u_hidden_dim (the RMS norms
-    divide by it).  max_steps: accepted steps per path; max_attempts: rounds of a tile, 2 max_steps unless given -- the kernel's
-    hard bound.  A path that ends at either gets status XW_DOPRI_STEPS (2); nothing is read back here, nothing raised for a status:
+    -- the state at t_end --, rec[cap,2,N] -- t0 and dt of each accepted step below cap --, ckpt[cap,H,N] -- the state at the
+    start of each accepted step below cap, slot 0 the lifted start value (include/xnwan_eval_grad.h; the same cap as rec's where
+    both are given) -- and fin[2,N] -- t0 and dt of every controller when it stopped); theta at the widths (H, K), the generic
+    layout; Hn: the network's u_hidden_dim (the RMS norms divide by it).  The same kernel and the same bits with and without ckpt:
+    xw_paths_dopri5_ckpt_fwd is called when a job of the launch has one, xw_paths_dopri5_fwd otherwise.
+    max_steps: accepted steps per path; max_attempts: rounds of a tile, 2 max_steps unless given -- the kernel's hard bound.  A path that ends at either gets status XW_DOPRI_STEPS (2); nothing is read back here, nothing raised for a status:
     the launch can be captured (the caller reads status, dopri5_status_message words it)."""
     _need_gpu()
     max_steps = int(max_steps)
@@ -763,8 +765,12 @@ def paths_dopri5_fwd(jobs, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATO
         raise XnwanError('paths_dopri5_fwd: max_steps and max_attempts must be >= 1')
     d = jobs[0]['xT'].shape[0]
     _chk(theta, F64, (theta_size(d, H, K),), 'theta')
-    arr = (XwPathsDopriJob * len(jobs))()
+    keep = any(j.get('ckpt') is not None for j in jobs)
+    arr = ((XwPathsDopriCkptJob if keep else XwPathsDopriJob) * len(jobs))()
     for a, j in zip(arr, jobs):
+        ckpt = j.get('ckpt')
+        if keep:
+            a.ckpt, a = _p(ckpt), a.f
         N = j['xT'].shape[1]
         _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start')
         _chk(j['t_in'], F64, (N,), 't_in'); _chk(j['t_end'], F64, (N,), 't_end'); _chk(j['u'], F64, (N,), 'u')
@@ -779,14 +785,61 @@ def paths_dopri5_fwd(jobs, theta, H, K, m, Hn, rtol=DOPRI5_RTOL, atol=DOPRI5_ATO
                 raise XnwanError('rec must have shape (cap, 2, %d), got %s' % (N, tuple(rec.shape)))
             cap = rec.shape[0]
             _chk(rec, F64, (cap, 2, N), 'rec')
+        if ckpt is not None:
+            if ckpt.dim() != 3 or ckpt.shape[0] < 1 or (rec is not None and ckpt.shape[0] != cap):
+                raise XnwanError('ckpt must have shape (cap, %d, %d) with cap >= 1%s, got %s'
+                                 % (H, N, '' if rec is None else " = rec's %d" % cap, tuple(ckpt.shape)))
+            cap = ckpt.shape[0]
+            _chk(ckpt, F64, (cap, H, N), 'ckpt')
         _chk(j.get('Y'), F64, (H, N), 'Y'); _chk(j.get('fin'), F64, (2, N), 'fin')
         a.xT, a.start, a.t_in, a.t_end, a.u = _p(j['xT']), _p(j['start']), _p(j['t_in']), _p(j['t_end']), _p(j['u'])
         a.status, a.n_acc, a.n_att = _p(j['status']), _p(j['n_acc']), _p(j['n_att'])
         a.Y, a.rec, a.fin, a.N, a.cap = _p(j.get('Y')), _p(rec), _p(j.get('fin')), N, cap
     # (xw_paths_dopri5_work is the tiled dopri5 forward's workspace, xw_tdopri5_work(0, ...): one allocation helper for both)
-    work = _dopri5_tiled_work(False, d, H, K, m, [a.N for a in arr], theta.device)
-    check(lib.xw_paths_dopri5_fwd(arr, len(jobs), _p(theta), d, H, K, m, int(Hn), float(rtol), float(atol), max_steps, max_attempts,
-                                  _p(work), _stream()), 'xw_paths_dopri5_fwd')
+    work = _dopri5_tiled_work(False, d, H, K, m, [j['xT'].shape[1] for j in jobs], theta.device)
+    entry = 'xw_paths_dopri5_ckpt_fwd' if keep else 'xw_paths_dopri5_fwd'
+    check(getattr(lib, entry)(arr, len(jobs), _p(theta), d, H, K, m, int(Hn), float(rtol), float(atol), max_steps, max_attempts,
+                              _p(work), _stream()), entry)
+
+
+def paths_dopri5_grad(jobs, theta, H, K, m):
+    """the reverse sweep behind paths_dopri5_fwd (csrc/xw_tdopri_paths_grad.hip, include/xnwan_eval_grad.h): job = dict(xT[d,N],
+    start[N], t_in[N], t_end[N] -- as the forward pass took them --, n_acc[N] int32, rec[cap,2,N] and ckpt[cap,H,N] as that forward
+    pass wrote them (every path with status 0 and n_acc <= cap), Y[H,N], its y(t_end), where ut is asked for, and the outputs asked
+    for, at least one of gx[d,N], gs[N], ut[N]).  With the cotangent 1 on every path's value u_p: gx = du_p/dx_p and gs =
+    du_p/dstart_p, the discrete adjoint (the exact reverse of the accepted steps, the recorded t0 and dt held fixed, the last step
+    through its dense output at t_end); ut = FL_w . F(t_end, x_p, Y_p), the time derivative of the CONTINUOUS model at fixed x -- not
+    the derivative of the discrete u with respect to the end of its grid.  Slots at or past a path's n_acc are never read.  Nothing
+    is read back: the launch can be captured."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    arr = (XwPathsDopriGradJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start')
+        _chk(j['t_in'], F64, (N,), 't_in'); _chk(j['t_end'], F64, (N,), 't_end')
+        for k in ('n_acc', 'rec', 'ckpt'):
+            if j.get(k) is None:
+                raise XnwanError('paths_dopri5_grad: %s, as paths_dopri5_fwd wrote it, is needed (the controller is not run again)' % k)
+        _chk(j['n_acc'], torch.int32, (N,), 'n_acc')
+        rec, ckpt = j['rec'], j['ckpt']
+        if rec.dim() != 3 or rec.shape[0] < 1:
+            raise XnwanError('rec must have shape (cap, 2, %d) with cap >= 1, got %s' % (N, tuple(rec.shape)))
+        cap = rec.shape[0]
+        _chk(rec, F64, (cap, 2, N), 'rec'); _chk(ckpt, F64, (cap, H, N), 'ckpt')
+        if j.get('gx') is None and j.get('gs') is None and j.get('ut') is None:
+            raise XnwanError('paths_dopri5_grad: no output requested (at least one of gx, gs, ut)')
+        if j.get('ut') is not None and j.get('Y') is None:
+            raise XnwanError('paths_dopri5_grad: ut needs Y [H, N], the forward pass\'s state at t_end')
+        _chk(j.get('Y'), F64, (H, N), 'Y')
+        _chk(j.get('gx'), F64, (d, N), 'gx'); _chk(j.get('gs'), F64, (N,), 'gs'); _chk(j.get('ut'), F64, (N,), 'ut')
+        a.xT, a.start, a.t_in, a.t_end = _p(j['xT']), _p(j['start']), _p(j['t_in']), _p(j['t_end'])
+        a.n_acc, a.rec, a.ckpt, a.Y = _p(j['n_acc']), _p(rec), _p(ckpt), _p(j.get('Y'))
+        a.gx, a.gs, a.ut, a.N, a.cap = _p(j.get('gx')), _p(j.get('gs')), _p(j.get('ut')), N, cap
+    # (xw_paths_dopri5_grad_work is the tiled dopri5 sweep's workspace, xw_tdopri5_work(1, ...): one allocation helper for both)
+    work = _dopri5_tiled_work(True, d, H, K, m, [a.N for a in arr], theta.device)
+    check(lib.xw_paths_dopri5_grad(arr, len(jobs), _p(theta), d, H, K, m, _p(work), _stream()), 'xw_paths_dopri5_grad')
 
 
 def dopri5_sweep(jobs, t, theta, H, K, m, want_x, want_params, x_cot_ones=False, stepper='vector'):

@@ -347,18 +347,28 @@ class XNODE(nn.Module):
         u: the bits of evaluate().  grad: du/dx of the discrete solution, every point's grid held fixed, the chain rule through the
         start value h([T0, x]) included (h is differentiated by autograd and taken to act point by point).  ut: FL_w . F(t, x, y(t)),
         the time derivative of the CONTINUOUS model at fixed x -- not the derivative of the discrete u with respect to the end time
-        of its grid.  Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, and points that
-        are not entered at T0 (the hourglass's re-entered points: their entry time depends on x).  chunk: paths per launch
-        (evalpaths.EVAL_CHUNK_PATHS, bounded further by the checkpoints' memory, evalpaths.EVAL_GRAD_CKPT_BYTES)."""
+        of its grid.  Solver 'dopri5': every point is one adaptive solve of its own, as in evaluate() (rtol, atol and
+        dopri5_max_steps of this module; n_sub must be None), run twice -- once for u and the step counts, once with a record and
+        checkpoints of exactly that size -- and grad is the reverse of every point's own accepted steps, step sizes held fixed, the
+        last step through its dense output at t (training's convention for dopri5).  Refused: the solver 'explicit_adams', a
+        domain class without `entry`, t < t_in, and points that are not entered at T0 (the hourglass's re-entered points: their
+        entry time depends on x).  chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS, bounded further by the checkpoints'
+        memory, evalpaths.EVAL_GRAD_CKPT_BYTES)."""
+        return self._evaluate_grad(points, n_sub, chunk, None)
+
+    def _evaluate_grad(self, points, n_sub, chunk, max_steps):
+        """evaluate_grad with dopri5's step limit given (NODE_WAN_solver passes its option; None: self.dopri5_max_steps)"""
         from . import evalpaths
         if self.blob is None:
             raise XnwanError('XNODE.bind(device) has not been called')
         self.blob.check_alias()
         dev = self.blob.data.device
+        adaptive = dict(tol=(self.rtol, self.atol), Hn=self.hidden_dim,
+                        max_steps=self.dopri5_max_steps if max_steps is None else max_steps) if self.method == KN.DOPRI5 else {}
         with torch.cuda.device(dev):
             return evalpaths.evaluate_points_grad(points, n_sub, self.setup, self.domain, self.solver, self.h, self.blob.data,
                                                   self.method, self.kdims[0], self.kdims[1], self.num_layers, dev,
-                                                  chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk)
+                                                  chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk, **adaptive)
 
     def forward(self, inputs, starts_at_T0=None):
         """starts_at_T0 (optional): the caller knows where the paths start -- True: at T0 (start values h), False: on the

@@ -287,12 +287,14 @@ class NODE_WAN_solver:
 
     def evaluate_grad(self, points, n_sub=None):
         """the trained solution, its gradient in x and its time derivative at scattered space-time points [M, 1 + d] (time first;
-        host or device) -> dict(u [M], grad [M, d], ut [M]) on the solver's device (XNODE.evaluate_grad: evaluate()'s grids, fixed-grid
-        solvers only).  u: the bits of evaluate(); grad: du/dx of the discrete solution with every point's grid held fixed, through
-        the start value h as well; ut: FL_w . F(t, x, y(t)), the time derivative of the continuous model at fixed x, not of the
-        discrete u in the end time of its grid.  Points that are not entered at T0 (the hourglass's re-entered points) are refused.
+        host or device) -> dict(u [M], grad [M, d], ut [M]) on the solver's device (XNODE.evaluate_grad: evaluate()'s grids for the
+        fixed-grid solvers; solver 'dopri5': one adaptive solve per point as in evaluate(), at most EngineOptions.dopri5_max_steps
+        accepted steps each, n_sub must be None; 'explicit_adams' is refused).  u: the bits of evaluate(); grad: du/dx of the
+        discrete solution with every point's grid -- dopri5: its accepted steps -- held fixed, through the start value h as well;
+        ut: FL_w . F(t, x, y(t)), the time derivative of the continuous model at fixed x, not of the discrete u in the end time of
+        its grid.  Points that are not entered at T0 (the hourglass's re-entered points) are refused.
         No collective calls (every rank evaluates what it is given), no random numbers drawn."""
-        return self.u_net.module.evaluate_grad(points, n_sub, chunk=self.options.eval_chunk_paths)
+        return self.u_net.module._evaluate_grad(points, n_sub, self.options.eval_chunk_paths, self.options.dopri5_max_steps)
 
     # --------------------------------------------------------------------------------------------------------------
     def _new_domain(self):
