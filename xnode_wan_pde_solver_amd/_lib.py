@@ -44,7 +44,12 @@ class XwPathsGradJob(ctypes.Structure):   # include/xnwan_grad.h: one ragged gro
                 ('N', c_int)]
 
 
-class XwPathsDopriCkptJob(ctypes.Structure):   # include/xnwan_eval_grad.h: XwPathsDopriJob with the checkpoints kept (f.cap slots)
+class XwPathsHvpJob(ctypes.Structure):    # include/xnwan_hess.h: one ragged group of xw_paths_tiled_hvp (XwPathsGradJob's inputs and a direction)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('tT', c_vp), ('nstep', c_vp), ('Y', c_vp), ('vx', c_vp), ('vs', c_vp), ('Yd', c_vp),
+                ('ju', c_vp), ('hx', c_vp), ('hs', c_vp), ('N', c_int)]
+
+
+class XwPathsDopriCkptJob(ctypes.Structure):  # include/xnwan_eval_grad.h: XwPathsDopriJob with the checkpoints kept (f.cap slots)
     _fields_ = [('f', XwPathsDopriJob), ('ckpt', c_vp)]
 
 
@@ -196,7 +201,14 @@ EVAL_GRAD_SIGNATURES = {
 }
 
 
-class XwSwitches(ctypes.Structure):      # include/xnwan_switches.h: the library's process-wide switches
+# the extension header include/xnwan_hess.h: same conventions
+HESS_SIGNATURES = {
+    'xw_paths_tiled_hvp_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_tiled_hvp': [ctypes.POINTER(XwPathsHvpJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p, c_vp],
+}
+
+
+class XwSwitches(ctypes.Structure):     # include/xnwan_switches.h: the library's process-wide switches
     _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
 
 
@@ -227,7 +239,7 @@ def _load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(GRAD_SIGNATURES.items())
-                           + list(EVAL_GRAD_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
+                           + list(EVAL_GRAD_SIGNATURES.items()) + list(HESS_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

@@ -18,7 +18,14 @@ with its checkpoints kept, then kernels.tiled_paths_grad (csrc/xw_tiled_paths_gr
 group, and the chain rule through the start value (start_gradient).  Its docstring says what its `ut` is and what it refuses.
 With solver 'dopri5' (tol given) it is three passes: paths_dopri5 for u and every path's step count, then, sorted by that count and
 cut by dopri5_grad_chunks, the same forward with its record and checkpoints kept and kernels.paths_dopri5_grad
-(csrc/xw_tdopri_paths_grad.hip), the reverse sweep over every path's own accepted steps (dopri5_grad_pass)."""
+(csrc/xw_tdopri_paths_grad.hip), the reverse sweep over every path's own accepted steps (dopri5_grad_pass).
+
+Second derivatives come from evaluate_points_hvp and evaluate_points_hess (behind evaluate_hvp / evaluate_hess of XNODE and
+NODE_WAN_solver), for the fixed-grid schemes: the forward and the gradient sweep as above, then kernels.tiled_paths_hvp
+(csrc/xw_tiled_paths_hvp.hip), the tangent of that sweep along a direction per point, once per direction over the same checkpoints,
+and the chain rule through the start value to second order (start_gradient, start_hvp)."""
+import types
+
 import torch
 
 from . import kernels as KN
@@ -291,6 +298,187 @@ def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method,
         inv = inverse.to(device)
         grad = gx.t()[inv] + gs[inv].view(-1, 1) * hx.to(device)
         return dict(u=u[inv], grad=grad.contiguous(), ut=ut[inv])
+
+
+def start_hvp(h, first, v):
+    """(d^2h/dx^2 . v) [M, d] at first = [t_in, x] ([M, 1 + d]) for directions v [M, d]: double backward on a leaf copy of `first`
+    -- the gradient of h(first).sum() with its graph kept, then the gradient of (that gradient . v).sum() -- the time column
+    dropped.  It rests on start_gradient's assumption: h acts POINT BY POINT, so the sums decouple row by row.  Exact zeros where h
+    or its gradient does not depend on its input (a constant h, an h that ignores x, an h that is linear in x)."""
+    zero = torch.zeros_like(first[:, 1:])
+    with torch.enable_grad():
+        leaf = first.detach().clone().requires_grad_(True)
+        out = h(leaf)
+        if not (torch.is_tensor(out) and out.requires_grad):
+            return zero
+        grad, = torch.autograd.grad(out.sum(), leaf, create_graph=True, allow_unused=True)
+        if grad is None or not grad.requires_grad:
+            return zero
+        hv, = torch.autograd.grad((grad[:, 1:] * v.detach().to(grad.dtype).to(grad.device)).sum(), leaf, allow_unused=True)
+    if hv is None:
+        return zero
+    return hv[:, 1:].detach().to(first.dtype)
+
+
+def hvp_chunk_paths(chunk, L, H):
+    """paths per launch of evaluate_points_hvp / evaluate_points_hess: the checkpoints Y and the tangent checkpoints Yd, [L, H, n]
+    each, stay below EVAL_GRAD_CKPT_BYTES together (whole 16-path tiles, at least one) -- a memory bound, not a tuned number"""
+    return min(chunk, max(16, 16 * (EVAL_GRAD_CKPT_BYTES // (2 * 8 * L * H * 16))))
+
+
+def second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk):
+    """the host side evaluate_points_hvp and evaluate_points_hess share, evaluate_points_grad's for the fixed-grid schemes: the
+    refusals (under the name `who`), the entry rule, the start values and their gradient, step counts, packing and sort.
+    -> None for an empty cloud, else a namespace of the sorted group on `device` and what puts results back"""
+    if solver in REFUSED_SOLVERS:
+        raise XnwanError("%s: solver %r is not served -- second derivatives at scattered points run the fixed-grid schemes %s only "
+                         "(the tangent of the reverse sweep over the steps taken; no per-path step controller or multistep history "
+                         "is differentiated twice)" % (who, solver, sorted(KN.METHODS)))
+    entry = getattr(domain, 'entry', None)
+    if entry is None:
+        name = getattr(domain, '__name__', type(domain).__name__)
+        raise XnwanError('%s: the domain class %s has no entry(points, shape_param, T0, T) rule: where a point\'s path '
+                         'starts, and with which start value, is the domain\'s to say' % (who, name))
+    d, T0, T = setup['dim'], setup['T0'], setup['T']
+    n_sub = setup['N_t'] if n_sub is None else n_sub
+    if n_sub < 1:
+        raise XnwanError('%s: n_sub = %r, at least one step over [T0, T]' % (who, n_sub))
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 1 + d):
+        raise XnwanError('%s: points must be a tensor [M, 1 + d] = [M, %d], time first' % (who, 1 + d))
+    pts = points.detach().to(F64)
+    if pts.shape[0] == 0:
+        return None
+    t = pts[:, 0].contiguous()
+    t_in, at_T0 = entry(pts, setup['shape_param'], T0, T)
+    early = t < t_in
+    if bool(early.any()):
+        i = int(early.nonzero()[0])
+        raise XnwanError('%s: %d points lie before their entry time (t >= t_in is the limit; first: point %d, '
+                         't = %r, t_in = %r)' % (who, int(early.sum()), i, float(t[i]), float(t_in[i])))
+    late = ~at_T0
+    if bool(late.any()):
+        i = int(late.nonzero()[0])
+        raise XnwanError('%s: %d points are not entered at T0 (entry at T0 is the limit; first: point %d, t = %r, '
+                         't_in = %r): their path starts on the moving boundary at a time that depends on x, and derivatives '
+                         'with that time held fixed are not those of u in x' % (who, int(late.sum()), i, float(t[i]), float(t_in[i])))
+    first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
+    s = h(first).reshape(-1).double()
+    n = step_counts(t, t_in, T0, T, n_sub)
+    order, inverse = sort_by_steps(n)
+    return types.SimpleNamespace(
+        M=pts.shape[0], d=d, first=first, dh=start_gradient(h, first).to(F64), order=order, inv=inverse.to(device),
+        tT=pack_grids(t[order], t_in[order], n[order]).to(device), xT=pts[order, 1:].t().contiguous().to(device),
+        start=s[order].contiguous().to(device), nstep=n[order].to(torch.int32).to(device))
+
+
+def second_order_pass(e, ndir, direction, theta, method, H, K, m, device, chunk, want_ju=False):
+    """per chunk of the sorted group e (second_order_entry): kernels.tiled_paths_fwd with its checkpoints kept,
+    kernels.tiled_paths_grad for gx and gs, then one kernels.tiled_paths_hvp launch per direction i < ndir over the same
+    checkpoints, the tangent checkpoints and the workspace shared by the directions.  direction(i, lo, k) -> (vxT [d, k], vs [k]),
+    contiguous on the device, for the chunk's paths lo .. lo + k of the sorted group: a direction exists for one chunk at a time.
+    -> (u [M], gx [d, M], gs [M], ju [ndir, M] or None, hx [ndir, d, M], hs [ndir, M]), sorted as e"""
+    M, d, L = e.M, e.d, e.tT.shape[0]
+    per = hvp_chunk_paths(chunk, L, H)
+    new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+    u, gx, gs = new(M), new(d, M), new(M)
+    ju, hx, hs = new(ndir, M) if want_ju else None, new(ndir, d, M), new(ndir, M)
+    for lo in range(0, M, per):
+        k = min(lo + per, M) - lo
+        whole = k == M
+        cut = (lambda a: a) if whole else (lambda a: a[:, lo:lo + k].contiguous())
+        job = dict(xT=cut(e.xT), start=e.start[lo:lo + k], tT=cut(e.tT), nstep=e.nstep[lo:lo + k], u=new(L, k), Y=new(L, H, k))
+        KN.tiled_paths_fwd([job], theta, method, H, K, m)
+        g = dict(gx=gx if whole else new(d, k), gs=gs[lo:lo + k])
+        KN.tiled_paths_grad([dict(job, **g)], theta, method, H, K, m)
+        u[lo:lo + k] = job['u'][L - 1]
+        if not whole:
+            gx[:, lo:lo + k] = g['gx']
+        Yd, work = new(L, H, k), KN.paths_hvp_work(d, H, K, m, (k + 15) // 16, device)
+        part = None if whole else new(d, k)
+        for i in range(ndir):
+            vxT, vs = direction(i, lo, k)
+            o = dict(vx=vxT, vs=vs, Yd=Yd, hx=hx[i] if whole else part, hs=hs[i, lo:lo + k])
+            if want_ju:
+                o['ju'] = ju[i, lo:lo + k]
+            KN.tiled_paths_hvp([dict(job, **o)], theta, method, H, K, m, work=work)
+            if not whole:
+                hx[i, :, lo:lo + k] = part
+    return u, gx, gs, ju, hx, hs
+
+
+def evaluate_points_hvp(points, v, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta, its gradient in x and its Hessian in x applied to a direction per point, at points [M, 1 + d] (time first; host or
+    device, float32 or float64) with v [M, d] -> dict(u [M], grad [M, d], dv [M], hvp [M, d]), float64 on `device`.  Entry rule,
+    step counts, packing, sort and refusals are evaluate_points_grad's; per chunk (hvp_chunk_paths) three launches: the forward
+    with its checkpoints kept, kernels.tiled_paths_grad, and kernels.tiled_paths_hvp with the direction (v, dh/dx . v):
+      u, grad  the bits of evaluate_points_grad
+      dv       grad . v, the directional derivative, from the tangent forward (ju)
+      hvp      d/dx (du/dx) . v of the DISCRETE solution x -> U(x, h([T0, x])) with every point's grid held fixed:
+               hx + hs dh/dx + gs (d^2h/dx^2 . v) (start_gradient, start_hvp: the chain rule through the start value); ReLU kinks
+               as autograd takes them.
+    Time is not perturbed.  Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, every
+    point that is not entered at T0, and a v of another shape than [M, d].  No collective calls, no random numbers."""
+    who = 'evaluate_hvp()'
+    with torch.no_grad():
+        e = second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk)
+        M, d = points.shape[0], setup['dim']
+        if not (torch.is_tensor(v) and tuple(v.shape) == (M, d)):
+            raise XnwanError('%s: v must be a tensor [M, d] = [%d, %d], a direction per point (got %s)'
+                             % (who, M, d, tuple(v.shape) if torch.is_tensor(v) else type(v).__name__))
+        if e is None:
+            new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+            return dict(u=new(0), grad=new(0, d), dv=new(0), hvp=new(0, d))
+        vv = v.detach().to(F64).to(e.first.device)
+        d2 = start_hvp(h, e.first, vv).to(F64).to(device)
+        dh = e.dh.to(device)
+        vd = vv.to(device)
+        od = e.order.to(device)
+        vxT, vs = vd[od].t().contiguous(), (dh * vd).sum(1)[od].contiguous()
+        direction = lambda i, lo, k: (vxT if k == M else vxT[:, lo:lo + k].contiguous(), vs[lo:lo + k])   # noqa: E731
+        u, gx, gs, ju, hx, hs = second_order_pass(e, 1, direction, theta, method, H, K, m, device, chunk, want_ju=True)
+        inv = e.inv
+        grad = gx.t()[inv] + gs[inv].view(-1, 1) * dh
+        hvp = hx[0].t()[inv] + hs[0][inv].view(-1, 1) * dh + gs[inv].view(-1, 1) * d2
+        return dict(u=u[inv], grad=grad.contiguous(), dv=ju[0][inv], hvp=hvp.contiguous())
+
+
+def evaluate_points_hess(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta, its gradient, its Hessian in x and its Laplacian at points [M, 1 + d] -> dict(u [M], grad [M, d], hess [M, d, d],
+    lap [M]), float64 on `device`.  evaluate_points_hvp's chain with d directions: per chunk the forward and the gradient run once,
+    then d launches of kernels.tiled_paths_hvp, v = e_k, over the same checkpoints; row k of hess is the k-th product,
+    hx_k + hs_k dh/dx + gs (d^2h/dx^2 . e_k).  hess is NOT symmetrised: its asymmetry is rounding, and a check.  lap is its trace.
+    Memory besides the chunk's checkpoints: the products as the launches write them ([d, d, M], the size of hess) and one unit
+    direction [d, chunk] that is refilled; d^2h/dx^2 . e_k is taken one k at a time.  Refusals: evaluate_points_hvp's."""
+    who = 'evaluate_hess()'
+    with torch.no_grad():
+        e = second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk)
+        d = setup['dim']
+        if e is None:
+            new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+            return dict(u=new(0), grad=new(0, d), hess=new(0, d, d), lap=new(0))
+        dh = e.dh.to(device)
+        dhs = dh[e.order.to(device)].t().contiguous()                # [d, M], sorted: row k is vs of direction e_k
+        unit = {}
+
+        def direction(i, lo, k):                                     # (refilled on the launches' stream, so in their order)
+            if unit.get('k') != k:
+                unit['k'], unit['e'] = k, torch.empty(d, k, dtype=F64, device=device)
+            unit['e'].zero_()
+            unit['e'][i].fill_(1.0)
+            return unit['e'], dhs[i, lo:lo + k]
+        u, gx, gs, _, hx, hs = second_order_pass(e, d, direction, theta, method, H, K, m, device, chunk)
+        inv = e.inv
+        gsi = gs[inv].view(-1, 1)
+        grad = gx.t()[inv] + gsi * dh
+        hess = hx.permute(2, 0, 1)[inv]                              # [M, d, d]: row k = hx of direction e_k
+        del hx
+        hess += hs.t()[inv].unsqueeze(2) * dh.unsqueeze(1)
+        eye = torch.eye(d, dtype=F64, device=e.first.device)
+        for k in range(d):
+            hess[:, k, :] += gsi * start_hvp(h, e.first, eye[k].expand(e.M, d)).to(F64).to(device)
+        return dict(u=u[inv], grad=grad.contiguous(), hess=hess.contiguous(), lap=torch.diagonal(hess, dim1=1, dim2=2).sum(1))
 
 
 def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS, tol=None,

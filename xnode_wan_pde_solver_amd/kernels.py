@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwPathsGradJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
+                   XwPathsGradJob, XwPathsHvpJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -527,6 +527,56 @@ def tiled_paths_grad(jobs, theta, method, H, K, m):
     # (xw_paths_tiled_grad_work is the sweep workspace of the family, xw_tiled_ode_work(1, ...): one allocation helper for both)
     work = tiled_ode_work(True, d, H, K, m, sum(lib.xw_tiled_ode_bwd_slabs(a.N) for a in arr), theta.device)
     check(lib.xw_paths_tiled_grad(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_grad')
+
+
+def paths_hvp_work(d, H, K, m, tiles, device):
+    """the workspace of one tiled_paths_hvp launch over `tiles` 16-path tiles (xw_paths_tiled_hvp_work doubles per tile: the
+    entry's own size, the gradient sweep's vectors and their tangents)"""
+    per = lib.xw_paths_tiled_hvp_work(d, H, K, m)
+    check(min(per, 0), 'xw_paths_tiled_hvp_work')
+    return torch.empty(per * tiles, dtype=F64, device=device)
+
+
+def tiled_paths_hvp(jobs, theta, method, H, K, m, work=None):
+    """Hessian-vector products behind tiled_paths_fwd (csrc/xw_tiled_paths_hvp.hip, include/xnwan_hess.h): job = dict(xT[d,N],
+    start[N], tT[L,N], optional nstep[N] int32, Y[L,H,N] -- as tiled_paths_grad takes them --, the direction vx[d,N] and vs[N], the
+    tangent checkpoints Yd[L,H,N] (scratch of the job that the caller allocates; every element is written: row l is the derivative of
+    y_l along the direction) and the outputs asked for, at least one of ju[N], hx[d,N], hs[N]).  With U_p(x, s) the DISCRETE final
+    value of path p, grid and step sizes held fixed: ju = dU_p/dx . vx_p + dU_p/ds vs_p, and (hx, hs) = the Hessian of U_p in (x, s)
+    applied to (vx_p, vs_p) -- the derivative of tiled_paths_grad's (gx, gs) along the direction, ReLU gates constants as autograd
+    takes them.  Time is not perturbed.  work: the launch's workspace (paths_hvp_work over the jobs' tiles) when the caller brings
+    its own.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsHvpJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        if j.get('Y') is None:
+            raise XnwanError('tiled_paths_hvp: Y [L, H, N], the checkpoints of tiled_paths_fwd, is needed (the forward is not recomputed)')
+        _chk(j['Y'], F64, (L, H, N), 'Y')
+        for k in ('vx', 'vs', 'Yd'):
+            if j.get(k) is None:
+                raise XnwanError('tiled_paths_hvp: %s is needed (the direction vx [d, N] and vs [N]; Yd [L, H, N], the tangent '
+                                 'checkpoints the launch writes)' % k)
+        _chk(j['vx'], F64, (d, N), 'vx'); _chk(j['vs'], F64, (N,), 'vs'); _chk(j['Yd'], F64, (L, H, N), 'Yd')
+        if j.get('ju') is None and j.get('hx') is None and j.get('hs') is None:
+            raise XnwanError('tiled_paths_hvp: no output requested (at least one of ju, hx, hs)')
+        _chk(j.get('ju'), F64, (N,), 'ju'); _chk(j.get('hx'), F64, (d, N), 'hx'); _chk(j.get('hs'), F64, (N,), 'hs')
+        a.xT, a.start, a.tT, a.nstep, a.Y = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep')), _p(j['Y'])
+        a.vx, a.vs, a.Yd, a.ju, a.hx, a.hs, a.N = _p(j['vx']), _p(j['vs']), _p(j['Yd']), _p(j.get('ju')), _p(j.get('hx')), _p(j.get('hs')), N
+    tiles = sum((a.N + 15) // 16 for a in arr)
+    if work is None:
+        work = paths_hvp_work(d, H, K, m, tiles, theta.device)
+    else:
+        _chk(work, F64, (lib.xw_paths_tiled_hvp_work(d, H, K, m) * tiles,), 'work')
+    check(lib.xw_paths_tiled_hvp(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_hvp')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

@@ -370,6 +370,36 @@ class XNODE(nn.Module):
                                                   self.method, self.kdims[0], self.kdims[1], self.num_layers, dev,
                                                   chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk, **adaptive)
 
+    def evaluate_hvp(self, points, v, n_sub=None, chunk=None):
+        """u_theta, its gradient in x and its Hessian in x applied to a direction per point, at scattered space-time points
+        [M, 1 + d] (time first; host or device) with v [M, d] -> dict(u [M], grad [M, d], dv [M], hvp [M, d]) on the network's
+        device (evalpaths.evaluate_points_hvp): evaluate_grad()'s grids and launches, then the tangent of its reverse sweep along
+        (v, dh/dx . v) over the same checkpoints.  u, grad: the bits of evaluate_grad().  dv = grad . v.  hvp: the derivative of
+        grad along v -- of the discrete solution x -> U(x, h([T0, x])), every point's grid held fixed, the chain rule through the
+        start value to second order (h is differentiated twice by autograd and taken to act point by point), ReLU kinks as
+        autograd takes them.  Time is not perturbed.  Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without
+        `entry`, t < t_in, points that are not entered at T0, a v of another shape.  chunk: paths per launch
+        (evalpaths.EVAL_CHUNK_PATHS, bounded further by the memory of the checkpoints and their tangents)."""
+        return self._evaluate_second('evaluate_points_hvp', (points, v, n_sub), chunk)
+
+    def evaluate_hess(self, points, n_sub=None, chunk=None):
+        """u_theta, its gradient, its Hessian in x and its Laplacian at scattered space-time points [M, 1 + d] ->
+        dict(u [M], grad [M, d], hess [M, d, d], lap [M]) on the network's device (evalpaths.evaluate_points_hess): evaluate_hvp()'s
+        chain with the d unit directions, the forward and the gradient sweep once per chunk; row k of hess is the product with
+        e_k.  hess is not symmetrised (its asymmetry is rounding); lap is its trace.  Refusals: evaluate_hvp()'s."""
+        return self._evaluate_second('evaluate_points_hess', (points, n_sub), chunk)
+
+    def _evaluate_second(self, name, args, chunk):
+        from . import evalpaths
+        if self.blob is None:
+            raise XnwanError('XNODE.bind(device) has not been called')
+        self.blob.check_alias()
+        dev = self.blob.data.device
+        with torch.cuda.device(dev):
+            return getattr(evalpaths, name)(*args, self.setup, self.domain, self.solver, self.h, self.blob.data, self.method,
+                                            self.kdims[0], self.kdims[1], self.num_layers, dev,
+                                            chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk)
+
     def forward(self, inputs, starts_at_T0=None):
         """starts_at_T0 (optional): the caller knows where the paths start -- True: at T0 (start values h), False: on the
         moving boundary (start values g; the sampler's late-entry groups).  Saves reading inputs[0, 0, 0] / max(w) back from the

@@ -296,6 +296,22 @@ class NODE_WAN_solver:
         No collective calls (every rank evaluates what it is given), no random numbers drawn."""
         return self.u_net.module._evaluate_grad(points, n_sub, self.options.eval_chunk_paths, self.options.dopri5_max_steps)
 
+    def evaluate_hvp(self, points, v, n_sub=None):
+        """the trained solution, its gradient in x and its Hessian in x applied to a direction per point, at scattered space-time
+        points [M, 1 + d] with v [M, d] -> dict(u [M], grad [M, d], dv [M], hvp [M, d]) on the solver's device
+        (XNODE.evaluate_hvp; the fixed-grid solvers: 'dopri5' and 'explicit_adams' are refused).  u and grad: the bits of
+        evaluate_grad(); dv = grad . v; hvp: the derivative of grad along v, of the discrete solution with every point's grid
+        held fixed, through the start value h as well.  Points that are not entered at T0 are refused.
+        No collective calls (every rank evaluates what it is given), no random numbers drawn."""
+        return self.u_net.module.evaluate_hvp(points, v, n_sub, chunk=self.options.eval_chunk_paths)
+
+    def evaluate_hess(self, points, n_sub=None):
+        """the trained solution, its gradient, its Hessian in x and its Laplacian at scattered space-time points [M, 1 + d] ->
+        dict(u [M], grad [M, d], hess [M, d, d], lap [M]) on the solver's device (XNODE.evaluate_hess: d Hessian-vector products
+        over one forward pass and one gradient sweep; hess is not symmetrised, lap is its trace).  Refusals: evaluate_hvp()'s.
+        No collective calls, no random numbers drawn."""
+        return self.u_net.module.evaluate_hess(points, n_sub, chunk=self.options.eval_chunk_paths)
+
     # --------------------------------------------------------------------------------------------------------------
     def _new_domain(self):
         s = self.setup
