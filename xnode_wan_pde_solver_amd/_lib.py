@@ -49,6 +49,11 @@ class XwPathsHvpJob(ctypes.Structure):    # include/xnwan_hess.h: one ragged gro
                 ('ju', c_vp), ('hx', c_vp), ('hs', c_vp), ('N', c_int)]
 
 
+class XwPathsJetJob(ctypes.Structure):    # include/xnwan_jet.h: one ragged group of xw_paths_tiled_jet (XwPathsJob's inputs, R curves per path, no Y)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('tT', c_vp), ('nstep', c_vp), ('vx', c_vp), ('vs', c_vp), ('qs', c_vp), ('u', c_vp),
+                ('ju', c_vp), ('quu', c_vp), ('N', c_int), ('R', c_int)]
+
+
 class XwPathsDopriCkptJob(ctypes.Structure):  # include/xnwan_eval_grad.h: XwPathsDopriJob with the checkpoints kept (f.cap slots)
     _fields_ = [('f', XwPathsDopriJob), ('ckpt', c_vp)]
 
@@ -208,7 +213,14 @@ HESS_SIGNATURES = {
 }
 
 
-class XwSwitches(ctypes.Structure):     # include/xnwan_switches.h: the library's process-wide switches
+# the extension header include/xnwan_jet.h: same conventions
+JET_SIGNATURES = {
+    'xw_paths_tiled_jet_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_tiled_jet': [ctypes.POINTER(XwPathsJetJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p, c_vp],
+}
+
+
+class XwSwitches(ctypes.Structure):    # include/xnwan_switches.h: the library's process-wide switches
     _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
 
 
@@ -239,7 +251,8 @@ def _load():
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(GRAD_SIGNATURES.items())
-                           + list(EVAL_GRAD_SIGNATURES.items()) + list(HESS_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
+                           + list(EVAL_GRAD_SIGNATURES.items()) + list(HESS_SIGNATURES.items()) + list(JET_SIGNATURES.items())
+                           + list(SWITCH_SIGNATURES.items())):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

@@ -23,7 +23,12 @@ cut by dopri5_grad_chunks, the same forward with its record and checkpoints kept
 Second derivatives come from evaluate_points_hvp and evaluate_points_hess (behind evaluate_hvp / evaluate_hess of XNODE and
 NODE_WAN_solver), for the fixed-grid schemes: the forward and the gradient sweep as above, then kernels.tiled_paths_hvp
 (csrc/xw_tiled_paths_hvp.hip), the tangent of that sweep along a direction per point, once per direction over the same checkpoints,
-and the chain rule through the start value to second order (start_gradient, start_hvp)."""
+and the chain rule through the start value to second order (start_gradient, start_hvp).
+
+Quadratic forms of the Hessian, the diffusion term sum a_ij d_ij u and the strong-form residual come from evaluate_points_quad,
+evaluate_points_lap and evaluate_points_residual (behind evaluate_quad / evaluate_lap of XNODE and NODE_WAN_solver and
+NODE_WAN_solver.evaluate_residual): kernels.tiled_paths_jet (csrc/xw_tiled_paths_jet.hip), a second-order forward jet along every
+point's own grid, R directions per point in one launch per chunk -- no reverse sweep, no checkpoints, no [M, d, d] output."""
 import types
 
 import torch
@@ -537,3 +542,181 @@ def evaluate_points(points, n_sub, setup, domain, solver, h, g, theta, method, H
         u = paths_forward(pts[order, 1:].t().contiguous().to(device), tT, s[order].contiguous().to(device),
                           n[order].to(torch.int32).to(device), theta, method, H, K, m, last_only=True, chunk=chunk)
         return u[inverse.to(device)]
+
+
+# ---- second-order forward jets: quadratic forms of the Hessian, the diffusion term and the strong-form residual ------------------------
+def jet_chunk_paths(chunk, R, work):
+    """paths per launch of evaluate_points_quad / evaluate_points_lap with R directions per path and `work` doubles of workspace per
+    block (kernels.paths_jet_work: a block per tile and direction): tiles * R * work * 8 <= EVAL_GRAD_CKPT_BYTES, whole 16-path
+    tiles, at least one -- a memory bound, not a tuned number.  There are no checkpoints: the workspace is what grows."""
+    return min(chunk, 16 * max(1, EVAL_GRAD_CKPT_BYTES // (8 * R * work)))
+
+
+def lap_directions(a, M, d, who='evaluate_lap()'):
+    """directions and weights (Q, lam) with sum_ij a_ij H_ij = sum_k lam_k q_k^T H q_k for every symmetric H: Q [R, d] and lam [R]
+    where one set serves all points, Q [M, R, d] and lam [M, R] where a point has its own; R = d, float64 on a's device (None: the
+    host).  a None: the unit directions with weights 1.  a [d, d] or [M, d, d] with every off-diagonal entry exactly zero: the unit
+    directions with weights a_kk.  Otherwise torch.linalg.eigh of the symmetric part (a_ij + a_ji) / 2 -- the antisymmetric part
+    contracts to zero with a Hessian --, on the host: rows q_k the eigenvectors, lam_k the eigenvalues; one decomposition for a
+    [d, d] matrix.  Another shape is refused."""
+    if a is None:
+        return torch.eye(d, dtype=F64), torch.ones(d, dtype=F64)
+    if not (torch.is_tensor(a) and tuple(a.shape) in ((d, d), (M, d, d))):
+        raise XnwanError('%s: a must be None (the Laplacian) or a tensor [d, d] = [%d, %d] or [M, d, d] = [%d, %d, %d] (got %s)'
+                         % (who, d, d, M, d, d, tuple(a.shape) if torch.is_tensor(a) else type(a).__name__))
+    A = a.detach().to(F64)
+    diag = torch.diagonal(A, dim1=-2, dim2=-1)
+    if bool(torch.all(A - torch.diag_embed(diag) == 0)):
+        return torch.eye(d, dtype=F64, device=A.device), diag.contiguous()
+    lam, Qm = torch.linalg.eigh((0.5 * (A + A.transpose(-1, -2))).cpu())
+    return Qm.transpose(-1, -2).contiguous().to(A.device), lam.to(A.device)
+
+
+def quad_pass(e, V, h, theta, method, H, K, m, device, chunk):
+    """kernels.tiled_paths_jet over the sorted group e (second_order_entry) with the directions V -- [R, d], one set for all points,
+    or [M, R, d], in the caller's order -- and the chain rule through the start value: per direction vs = dh/dx . v and
+    qs = v . (d^2h/dx^2 . v) (start_gradient, start_hvp).  Per chunk (jet_chunk_paths) ONE launch, a block per tile and direction.
+    -> (u [M], ju [R, M], quu [R, M]), in the caller's order"""
+    M, d, R = e.M, e.d, V.shape[-2]
+    shared = V.dim() == 2
+    Vh = V.detach().to(F64).to(e.first.device)
+    vs, qs = [], []
+    for r in range(R):
+        v = Vh[r].expand(M, d) if shared else Vh[:, r]
+        vs.append((e.dh * v).sum(1))
+        qs.append((v * start_hvp(h, e.first, v).to(F64)).sum(1))
+    od = e.order.to(device)
+    vs, qs = torch.stack(vs)[:, e.order].contiguous().to(device), torch.stack(qs)[:, e.order].contiguous().to(device)
+    Vd = Vh.to(device)
+    doubles = KN.lib.xw_paths_tiled_jet_work(d, H, K, m)
+    KN.check(min(doubles, 0), 'xw_paths_tiled_jet_work')
+    per = jet_chunk_paths(chunk, R, doubles)
+    new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+    u, ju, quu = new(M), new(R, M), new(R, M)
+    work, vx = None, None
+    for lo in range(0, M, per):
+        k = min(lo + per, M) - lo
+        whole = k == M
+        cut = (lambda a: a) if whole else (lambda a: a[:, lo:lo + k].contiguous())
+        if not shared:
+            vx = Vd[od[lo:lo + k]].permute(1, 2, 0).contiguous()
+        elif vx is None or vx.shape[2] != k:
+            vx = Vd.unsqueeze(2).expand(R, d, k).contiguous()
+        if work is None or work.numel() != doubles * R * ((k + 15) // 16):   # (the chunks share it: they share the stream)
+            work = KN.paths_jet_work(d, H, K, m, R * ((k + 15) // 16), device)
+        out = dict(u=u[lo:lo + k], ju=ju if whole else new(R, k), quu=quu if whole else new(R, k))
+        KN.tiled_paths_jet([dict(xT=cut(e.xT), start=e.start[lo:lo + k], tT=cut(e.tT), nstep=e.nstep[lo:lo + k], vx=vx, vs=cut(vs),
+                                 qs=cut(qs), **out)], theta, method, H, K, m, work=work)
+        if not whole:
+            ju[:, lo:lo + k], quu[:, lo:lo + k] = out['ju'], out['quu']
+    return u[e.inv], ju[:, e.inv], quu[:, e.inv]
+
+
+def evaluate_points_quad(points, V, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta and, along R directions per point, its first and second directional derivatives in x, at points [M, 1 + d] (time
+    first; host or device, float32 or float64) with V [M, R, d] -> dict(u [M], dv [M, R], quad [M, R]), float64 on `device`.  Entry
+    rule, step counts, packing, sort and refusals are evaluate_points_hvp's (second_order_entry); per chunk (jet_chunk_paths) ONE
+    launch of kernels.tiled_paths_jet, a second-order forward jet: no reverse sweep, no checkpoints, nothing of size [M, d, d].
+      u     the kernel's own, the bits of evaluate_points (the jet's primal runs the forward's step text on the forward's blocks)
+      dv    grad . v_r, the directional derivative
+      quad  v_r^T (d^2u/dx^2) v_r of the DISCRETE solution x -> U(x, h([T0, x])) with every point's grid held fixed: the second
+            derivative of eps -> U(x + eps v, h(x + eps v)) at 0, the chain rule through the start value to second order
+            (vs = dh/dx . v, qs = v . d^2h/dx^2 v); ReLU kinks as autograd takes them.
+    Time is not perturbed.  Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, every
+    point that is not entered at T0, and a V of another shape than [M, R, d] with R >= 1.  No collective calls, no random numbers."""
+    who = 'evaluate_quad()'
+    with torch.no_grad():
+        e = second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk)
+        M, d = points.shape[0], setup['dim']
+        if not (torch.is_tensor(V) and V.dim() == 3 and V.shape[0] == M and V.shape[1] >= 1 and V.shape[2] == d):
+            raise XnwanError('%s: V must be a tensor [M, R, d] = [%d, R, %d], R >= 1 directions per point (got %s)'
+                             % (who, M, d, tuple(V.shape) if torch.is_tensor(V) else type(V).__name__))
+        R = V.shape[1]
+        if e is None:
+            new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+            return dict(u=new(0), dv=new(0, R), quad=new(0, R))
+        u, ju, quu = quad_pass(e, V, h, theta, method, H, K, m, device, chunk)
+        return dict(u=u, dv=ju.t().contiguous(), quad=quu.t().contiguous())
+
+
+def evaluate_points_lap(points, a, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS,
+                        who='evaluate_lap()'):
+    """u_theta and the diffusion term lap = sum_ij a_ij d^2u/dx_i dx_j at points [M, 1 + d] -> dict(u [M], lap [M]), float64 on
+    `device`: evaluate_points_quad's launch with the d directions and weights of lap_directions(a) -- a None: the Laplacian, the
+    unit directions; a [d, d] or [M, d, d] (the coefficient tabulated per point) with exactly zero off-diagonal entries: the unit
+    directions weighted by a_kk; otherwise the eigenvectors and eigenvalues of its symmetric part -- and lap = sum_k lam_k quad_k.
+    Derivatives of the DISCRETE solution with every point's grid held fixed, as evaluate_points_quad states them; the route of
+    evaluate_points_hess without the reverse sweeps, the checkpoints and the [M, d, d] output.  Refusals: evaluate_points_quad's,
+    and an `a` of another shape."""
+    with torch.no_grad():
+        e = second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk)
+        M, d = points.shape[0], setup['dim']
+        Q, lam = lap_directions(a, M, d, who)
+        if e is None:
+            return dict(u=torch.empty(0, dtype=F64, device=device), lap=torch.empty(0, dtype=F64, device=device))
+        u, _, quu = quad_pass(e, Q, h, theta, method, H, K, m, device, chunk)
+        lam = lam.to(device)
+        lap = (quu * (lam.view(-1, 1) if lam.dim() == 1 else lam.t())).sum(0)
+        return dict(u=u, lap=lap)
+
+
+def divergence_a(func_a, X, d):
+    """(div a)_j = sum_i d a_ij / d x_i on X [M, 1, 1 + d] -> [M, d], float64 on X's device: torch.autograd.grad of
+    func_a(leaf, i, j).sum() with respect to a leaf copy of X, entry by entry (the callable is taken to act POINT BY POINT, as
+    start_gradient takes h).  Exact zeros where an entry does not depend on X (no grad_fn, or an unused input)."""
+    M = X.shape[0]
+    div = torch.zeros(M, d, dtype=F64, device=X.device)
+    with torch.enable_grad():
+        leaf = X.detach().clone().requires_grad_(True)
+        for i in range(d):
+            for j in range(d):
+                out = func_a(leaf, i, j)
+                if not (torch.is_tensor(out) and out.requires_grad):
+                    continue
+                grad, = torch.autograd.grad(out.sum(), leaf, allow_unused=True)
+                if grad is not None:
+                    div[:, j] += grad.detach().reshape(M, -1)[:, 1 + i].to(F64)
+    return div
+
+
+def evaluate_points_residual(points, funcs, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS,
+                             div_a='autograd'):
+    """the strong-form residual of u_theta at points [M, 1 + d], for the PDE as the configs state it,
+        du/dt - sum_i d_i (sum_j a_ij d_j u) + b . grad u + c u = f,   c = func_c(X, u):
+    -> dict(u [M], ut [M], grad [M, d], diffusion [M], residual [M]), float64 on `device`, with
+        residual = ut - diffusion - (div a) . grad + b . grad + c u - f,   diffusion = sum_ij a_ij d^2u/dx_i dx_j.
+    funcs: dict(a, b, c, f) in the reference's callable protocol (func_a(X, i, j), func_b(X, i), func_f(X) -> [M, 1],
+    func_c(X, u) -> [M, 1, 1]), tabulated in float64 on X = points.view(M, 1, 1 + d), where the points live.  u, ut and grad are
+    evaluate_points_grad's, bit for bit; diffusion is evaluate_points_lap's with the tabulated a.  (div a)_j = sum_i d_i a_ij comes
+    from autograd through func_a (divergence_a: exact zeros where an entry does not depend on X) unless div_a is a callable
+    div_a(X, j) -> [M, 1].
+    What the derivatives are: ut is the time derivative of the CONTINUOUS model, FL_w . F(t, x, y(t)); grad and diffusion are
+    derivatives in x of the DISCRETE solution with every point's grid held fixed, as evaluate_points_grad documents -- the residual
+    mixes the two and is a check of the trained u, not an identity of the scheme.  The reference's loss carries the source term as
+    + f phi "as written"; the residual does not follow that sign: it is the PDE's, f on the right-hand side.
+    Refusals: evaluate_points_quad's, under this function's name; a div_a that is neither 'autograd' nor callable."""
+    who = 'evaluate_residual()'
+    if not (div_a == 'autograd' or callable(div_a)):
+        raise XnwanError("%s: div_a must be 'autograd' or a callable div_a(X, j) (got %r)" % (who, div_a))
+    with torch.no_grad():
+        d = setup['dim']
+        if second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk) is None:
+            new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+            return dict(u=new(0), ut=new(0), grad=new(0, d), diffusion=new(0), residual=new(0))
+        M = points.shape[0]
+        X = points.detach().to(F64).view(M, 1, 1 + d)
+        tab = lambda out: out.detach().to(F64).reshape(M).to(device)   # noqa: E731
+        A = torch.stack([torch.stack([tab(funcs['a'](X, i, j)) for j in range(d)], 1) for i in range(d)], 1)     # [M, d, d]
+        B = torch.stack([tab(funcs['b'](X, i)) for i in range(d)], 1)                                            # [M, d]
+        if callable(div_a):
+            D = torch.stack([tab(div_a(X, j)) for j in range(d)], 1)
+        else:
+            D = divergence_a(funcs['a'], X, d).to(device)
+        g = evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=chunk)
+        diffusion = evaluate_points_lap(points, A, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=chunk,
+                                        who=who)['lap']
+        u, ut, grad = g['u'], g['ut'], g['grad']
+        c = tab(funcs['c'](X, u.to(X.device).view(M, 1, 1)))
+        f = tab(funcs['f'](X))
+        residual = ut - diffusion - (D * grad).sum(1) + (B * grad).sum(1) + c * u - f
+        return dict(u=u, ut=ut, grad=grad, diffusion=diffusion, residual=residual)

@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwPathsGradJob, XwPathsHvpJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
+                   XwPathsGradJob, XwPathsHvpJob, XwPathsJetJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -577,6 +577,56 @@ def tiled_paths_hvp(jobs, theta, method, H, K, m, work=None):
     else:
         _chk(work, F64, (lib.xw_paths_tiled_hvp_work(d, H, K, m) * tiles,), 'work')
     check(lib.xw_paths_tiled_hvp(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_hvp')
+
+
+def paths_jet_work(d, H, K, m, blocks, device):
+    """the workspace of one tiled_paths_jet launch over `blocks` blocks, the jobs' sum of R * ((N + 15) // 16)
+    (xw_paths_tiled_jet_work doubles per block: the sweep's vectors, which keep every layer's gates, and the second order's)"""
+    per = lib.xw_paths_tiled_jet_work(d, H, K, m)
+    check(min(per, 0), 'xw_paths_tiled_jet_work')
+    return torch.empty(per * blocks, dtype=F64, device=device)
+
+
+def tiled_paths_jet(jobs, theta, method, H, K, m, work=None):
+    """second-order forward jets behind tiled_paths_fwd's inputs (csrc/xw_tiled_paths_jet.hip, include/xnwan_jet.h): job =
+    dict(xT[d,N], start[N], tT[L,N], optional nstep[N] int32 -- as tiled_paths_fwd takes them; NO checkpoints --, R curves per path
+    vx[R,d,N], vs[R,N] and optional qs[R,N] (None: zeros), and the outputs asked for: optional u[N], at least one of ju[R,N],
+    quu[R,N]).  With U_p(x, s) the DISCRETE final value of path p, grid and step sizes held fixed, along
+    gamma(eps) = (x + eps vx, s + eps vs + eps^2 / 2 qs): ju = d/deps U(gamma) = dU/dx . vx + dU/ds vs and quu = d^2/deps^2
+    U(gamma) = (vx, vs)^T Hess U (vx, vs) + dU/ds qs at eps = 0, ReLU gates constants as autograd takes them; u = U_p, the bits of
+    tiled_paths_fwd.  Time is not perturbed.  work: the launch's workspace (paths_jet_work over the jobs' blocks) when the caller
+    brings its own.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    _chk(theta, F64, (theta_size(d, H, K),), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsJetJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        for k in ('vx', 'vs'):
+            if j.get(k) is None:
+                raise XnwanError('tiled_paths_jet: %s is needed (the directions vx [R, d, N] and vs [R, N])' % k)
+        if not (torch.is_tensor(j['vx']) and j['vx'].dim() == 3 and j['vx'].shape[0] >= 1):
+            raise XnwanError('tiled_paths_jet: vx must be a tensor [R, d, N] with R >= 1 directions per path')
+        R = j['vx'].shape[0]
+        _chk(j['vx'], F64, (R, d, N), 'vx'); _chk(j['vs'], F64, (R, N), 'vs'); _chk(j.get('qs'), F64, (R, N), 'qs')
+        if j.get('ju') is None and j.get('quu') is None:
+            raise XnwanError('tiled_paths_jet: no output requested (at least one of ju, quu)')
+        _chk(j.get('u'), F64, (N,), 'u'); _chk(j.get('ju'), F64, (R, N), 'ju'); _chk(j.get('quu'), F64, (R, N), 'quu')
+        a.xT, a.start, a.tT, a.nstep = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep'))
+        a.vx, a.vs, a.qs, a.N, a.R = _p(j['vx']), _p(j['vs']), _p(j.get('qs')), N, R
+        a.u, a.ju, a.quu = _p(j.get('u')), _p(j.get('ju')), _p(j.get('quu'))
+    blocks = sum(a.R * ((a.N + 15) // 16) for a in arr)
+    if work is None:
+        work = paths_jet_work(d, H, K, m, blocks, theta.device)
+    else:
+        _chk(work, F64, (lib.xw_paths_tiled_jet_work(d, H, K, m) * blocks,), 'work')
+    check(lib.xw_paths_tiled_jet(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_jet')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

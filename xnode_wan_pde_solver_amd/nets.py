@@ -389,7 +389,26 @@ class XNODE(nn.Module):
         e_k.  hess is not symmetrised (its asymmetry is rounding); lap is its trace.  Refusals: evaluate_hvp()'s."""
         return self._evaluate_second('evaluate_points_hess', (points, n_sub), chunk)
 
-    def _evaluate_second(self, name, args, chunk):
+    def evaluate_quad(self, points, V, n_sub=None, chunk=None):
+        """u_theta and its first and second directional derivatives in x along R directions per point, at scattered space-time
+        points [M, 1 + d] (time first; host or device) with V [M, R, d] -> dict(u [M], dv [M, R], quad [M, R]) on the network's
+        device (evalpaths.evaluate_points_quad): ONE launch per chunk, a second-order forward jet along every point's own grid --
+        no reverse sweep, no checkpoints.  u: the bits of evaluate().  dv = grad . v_r.  quad = v_r^T (d^2u/dx^2) v_r of the
+        discrete solution x -> U(x, h([T0, x])), every point's grid held fixed, the chain rule through the start value to second
+        order, ReLU kinks as autograd takes them.  Time is not perturbed.  Refusals: evaluate_hvp()'s, and a V of another shape.
+        chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS, bounded further by the workspace's memory, a block per tile and
+        direction)."""
+        return self._evaluate_second('evaluate_points_quad', (points, V, n_sub), chunk)
+
+    def evaluate_lap(self, points, a=None, n_sub=None, chunk=None):
+        """u_theta and the diffusion term sum_ij a_ij d^2u/dx_i dx_j at scattered space-time points [M, 1 + d] ->
+        dict(u [M], lap [M]) on the network's device (evalpaths.evaluate_points_lap): evaluate_quad()'s launch with d directions --
+        a None: the Laplacian; a [d, d] or [M, d, d]: the unit directions weighted by a_kk where a is diagonal, else the
+        eigenvectors and eigenvalues of its symmetric part.  Derivatives of the discrete solution, every point's grid held fixed;
+        evaluate_hess()'s `lap` without the [M, d, d] output.  Refusals: evaluate_quad()'s, and an `a` of another shape."""
+        return self._evaluate_second('evaluate_points_lap', (points, a, n_sub), chunk)
+
+    def _evaluate_second(self, name, args, chunk, **kw):
         from . import evalpaths
         if self.blob is None:
             raise XnwanError('XNODE.bind(device) has not been called')
@@ -398,7 +417,7 @@ class XNODE(nn.Module):
         with torch.cuda.device(dev):
             return getattr(evalpaths, name)(*args, self.setup, self.domain, self.solver, self.h, self.blob.data, self.method,
                                             self.kdims[0], self.kdims[1], self.num_layers, dev,
-                                            chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk)
+                                            chunk=evalpaths.EVAL_CHUNK_PATHS if chunk is None else chunk, **kw)
 
     def forward(self, inputs, starts_at_T0=None):
         """starts_at_T0 (optional): the caller knows where the paths start -- True: at T0 (start values h), False: on the

@@ -312,6 +312,36 @@ class NODE_WAN_solver:
         No collective calls, no random numbers drawn."""
         return self.u_net.module.evaluate_hess(points, n_sub, chunk=self.options.eval_chunk_paths)
 
+    def evaluate_quad(self, points, V, n_sub=None):
+        """the trained solution and its first and second directional derivatives in x along R directions per point, at scattered
+        space-time points [M, 1 + d] with V [M, R, d] -> dict(u [M], dv [M, R], quad [M, R]) on the solver's device
+        (XNODE.evaluate_quad: a second-order forward jet, one launch per chunk, no reverse sweep and no checkpoints; the fixed-grid
+        solvers).  u: the bits of evaluate(); dv = grad . v_r; quad = v_r^T (d^2u/dx^2) v_r of the discrete solution with every
+        point's grid held fixed, through the start value h as well.  Refusals: evaluate_hvp()'s, and a V of another shape.
+        No collective calls, no random numbers drawn."""
+        return self.u_net.module.evaluate_quad(points, V, n_sub, chunk=self.options.eval_chunk_paths)
+
+    def evaluate_lap(self, points, a=None, n_sub=None):
+        """the trained solution and the diffusion term sum_ij a_ij d^2u/dx_i dx_j at scattered space-time points [M, 1 + d] ->
+        dict(u [M], lap [M]) on the solver's device (XNODE.evaluate_lap: a None is the Laplacian; a [d, d] or [M, d, d] a
+        coefficient, one for all points or tabulated per point).  Derivatives of the discrete solution with every point's grid
+        held fixed; what evaluate_hess()'s `lap` gives, without the Hessian.  Refusals: evaluate_quad()'s, and an `a` of another
+        shape.  No collective calls, no random numbers drawn."""
+        return self.u_net.module.evaluate_lap(points, a, n_sub, chunk=self.options.eval_chunk_paths)
+
+    def evaluate_residual(self, points, n_sub=None, div_a='autograd'):
+        """the strong-form residual of the trained solution at scattered space-time points [M, 1 + d], for the PDE
+        du/dt - sum_i d_i (sum_j a_ij d_j u) + b . grad u + c u = f with the solver's own func_a, func_b, func_c, func_f ->
+        dict(u [M], ut [M], grad [M, d], diffusion [M], residual [M]) on the solver's device (evalpaths.evaluate_points_residual):
+        residual = ut - diffusion - (div a) . grad + b . grad + c u - f.  u, ut, grad: the bits of evaluate_grad(); diffusion:
+        evaluate_lap() with a tabulated on the points; div a by autograd through func_a unless div_a(X, j) is given.  ut is the
+        CONTINUOUS model's time derivative, the space derivatives are those of the DISCRETE solution with every point's grid
+        held fixed, as evaluate_grad() documents.  The reference's loss carries + f phi "as written"; the residual does not follow it.
+        Refusals: evaluate_quad()'s.  No collective calls, no random numbers drawn."""
+        funcs = dict(a=self.func_a, b=self.func_b, c=self.func_c, f=self.func_f)
+        return self.u_net.module._evaluate_second('evaluate_points_residual', (points, funcs, n_sub), self.options.eval_chunk_paths,
+                                                  div_a=div_a)
+
     # --------------------------------------------------------------------------------------------------------------
     def _new_domain(self):
         s = self.setup
