@@ -28,7 +28,11 @@ and the chain rule through the start value to second order (start_gradient, star
 Quadratic forms of the Hessian, the diffusion term sum a_ij d_ij u and the strong-form residual come from evaluate_points_quad,
 evaluate_points_lap and evaluate_points_residual (behind evaluate_quad / evaluate_lap of XNODE and NODE_WAN_solver and
 NODE_WAN_solver.evaluate_residual): kernels.tiled_paths_jet (csrc/xw_tiled_paths_jet.hip), a second-order forward jet along every
-point's own grid, R directions per point in one launch per chunk -- no reverse sweep, no checkpoints, no [M, d, d] output."""
+point's own grid, R directions per point in one launch per chunk -- no reverse sweep, no checkpoints, no [M, d, d] output.
+
+Parameter gradients come from evaluate_points_vjp (behind XNODE.evaluate_vjp / evaluate_fn and NODE_WAN_solver.evaluate_vjp), for
+the fixed-grid schemes: the forward with its checkpoints kept, then kernels.tiled_paths_vjp (csrc/xw_tiled_paths_vjp.hip), the
+gradient sweep with a weight per point that writes a slab per tile, and kernels.slab_sum into one flat gradient, chunk by chunk."""
 import types
 
 import torch
@@ -303,6 +307,102 @@ def evaluate_points_grad(points, n_sub, setup, domain, solver, h, theta, method,
         inv = inverse.to(device)
         grad = gx.t()[inv] + gs[inv].view(-1, 1) * hx.to(device)
         return dict(u=u[inv], grad=grad.contiguous(), ut=ut[inv])
+
+
+# ---- parameter gradients: a weighted sum over the cloud of dU_p/dtheta -------------------------------------------------------------
+def vjp_chunk_paths(chunk, L, H, P):
+    """paths per launch of evaluate_points_vjp: a chunk's checkpoints Y [L, H, n] and its slabs [tiles, P] (P = theta's size) stay
+    below EVAL_GRAD_CKPT_BYTES together, 8 (L H n + P tiles) with n = 16 tiles (whole 16-path tiles, at least one) -- a memory
+    bound, not a tuned number.  At wide networks the slabs are the larger term: about 2 MB per tile at (256, 256)."""
+    return min(chunk, 16 * max(1, EVAL_GRAD_CKPT_BYTES // (8 * (16 * L * H + P))))
+
+
+def vjp_refuse_solver(solver):
+    """XnwanError for the solvers evaluate_points_vjp does not serve (XNODE.evaluate_fn asks before its forward runs)"""
+    if solver in REFUSED_SOLVERS:
+        raise XnwanError("evaluate_vjp(): solver %r is not served -- parameter gradients at scattered points run the fixed-grid "
+                         "schemes %s only (the reverse of the steps taken, with slabs; no per-path record sweep with slabs or "
+                         "multistep history is built)" % (solver, sorted(KN.METHODS)))
+
+
+def evaluate_points_vjp(points, w, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):
+    """u_theta at points [M, 1 + d] (time first; host or device, float32 or float64) and the weighted sum of its PARAMETER gradients,
+    with weights w [M] -> dict(u [M], gflat [P_u], start [M]), float64 on `device`.  Entry rule, step counts, packing, sort and
+    refusals are evaluate_points_grad's; per chunk (vjp_chunk_paths) kernels.tiled_paths_fwd keeps the checkpoints,
+    kernels.tiled_paths_vjp walks them back and kernels.slab_sum adds the chunk's slabs to gflat:
+      u      the forward's last row: the bits of evaluate_points
+      gflat  sum_p w_p dU_p/dtheta in theta's layout (P_u = theta's size), U_p the DISCRETE solution at point p: the exact reverse
+             of the steps taken, every point's grid and step sizes held fixed, the start value h([T0, x]) a constant of theta, ReLU
+             kinks as autograd takes them.  The chunks go in sorted order, so its bits are a function of the inputs and `chunk`.
+             Exact zeros for an empty cloud.
+      start  w_p dU_p/dstart_p, the cotangent that reaches every point's start value (h itself is not differentiated)
+    Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, every point that is not entered
+    at T0 -- its start value g does not depend on theta either, but one rule holds for all gradients at scattered points --, and a
+    w of another shape than [M].  No collective calls, no random numbers."""
+    who = 'evaluate_vjp()'
+    vjp_refuse_solver(solver)
+    entry = getattr(domain, 'entry', None)
+    if entry is None:
+        name = getattr(domain, '__name__', type(domain).__name__)
+        raise XnwanError('%s: the domain class %s has no entry(points, shape_param, T0, T) rule: where a point\'s path '
+                         'starts, and with which start value, is the domain\'s to say' % (who, name))
+    d, T0, T = setup['dim'], setup['T0'], setup['T']
+    n_sub = setup['N_t'] if n_sub is None else n_sub
+    if n_sub < 1:
+        raise XnwanError('%s: n_sub = %r, at least one step over [T0, T]' % (who, n_sub))
+    if chunk < 1:
+        raise XnwanError('eval_chunk_paths = %d: at least one path per launch' % chunk)
+    if not (torch.is_tensor(points) and points.dim() == 2 and points.shape[1] == 1 + d):
+        raise XnwanError('%s: points must be a tensor [M, 1 + d] = [M, %d], time first' % (who, 1 + d))
+    M = points.shape[0]
+    if not (torch.is_tensor(w) and tuple(w.shape) == (M,)):
+        raise XnwanError('%s: w must be a tensor [M] = [%d], a weight per point (got %s)'
+                         % (who, M, tuple(w.shape) if torch.is_tensor(w) else type(w).__name__))
+    P = KN.theta_size(d, H, K)
+    with torch.no_grad():
+        pts = points.detach().to(F64)
+        gflat = torch.zeros(P, dtype=F64, device=device)
+        if M == 0:
+            return dict(u=torch.empty(0, dtype=F64, device=device), gflat=gflat, start=torch.empty(0, dtype=F64, device=device))
+        t = pts[:, 0].contiguous()
+        t_in, at_T0 = entry(pts, setup['shape_param'], T0, T)
+        early = t < t_in
+        if bool(early.any()):
+            i = int(early.nonzero()[0])
+            raise XnwanError('%s: %d points lie before their entry time (t >= t_in is the limit; first: point %d, '
+                             't = %r, t_in = %r)' % (who, int(early.sum()), i, float(t[i]), float(t_in[i])))
+        late = ~at_T0
+        if bool(late.any()):
+            i = int(late.nonzero()[0])
+            raise XnwanError('%s: %d points are not entered at T0 (entry at T0 is the limit; first: point %d, t = %r, '
+                             't_in = %r): their path starts on the moving boundary; the start value there does not depend on theta, '
+                             'but gradients at scattered points keep one rule, evaluate_grad()\'s'
+                             % (who, int(late.sum()), i, float(t[i]), float(t_in[i])))
+        first = torch.cat((t_in.view(-1, 1), pts[:, 1:]), 1)
+        s = h(first).reshape(-1).double()
+        n = step_counts(t, t_in, T0, T, n_sub)
+        order, inverse = sort_by_steps(n)
+        tT = pack_grids(t[order], t_in[order], n[order]).to(device)
+        xT = pts[order, 1:].t().contiguous().to(device)
+        start, nstep = s[order].contiguous().to(device), n[order].to(torch.int32).to(device)
+        ws = w.detach().to(F64).to(order.device)[order].contiguous().to(device)
+        L = tT.shape[0]
+        per = vjp_chunk_paths(chunk, L, H, P)
+        u = torch.empty(M, dtype=F64, device=device)
+        gs = torch.empty(M, dtype=F64, device=device)
+        for lo in range(0, M, per):
+            k = min(lo + per, M) - lo
+            whole = k == M
+            job = dict(xT=xT if whole else xT[:, lo:lo + k].contiguous(), start=start[lo:lo + k],
+                       tT=tT if whole else tT[:, lo:lo + k].contiguous(), nstep=nstep[lo:lo + k],
+                       u=torch.empty(L, k, dtype=F64, device=device), Y=torch.empty(L, H, k, dtype=F64, device=device))
+            KN.tiled_paths_fwd([job], theta, method, H, K, m)
+            gslab = torch.empty((k + 15) // 16, P, dtype=F64, device=device)
+            KN.tiled_paths_vjp([dict(job, w=ws[lo:lo + k], gslab=gslab, gs=gs[lo:lo + k])], theta, method, H, K, m)
+            KN.slab_sum(gslab, out=gflat, accumulate=True)
+            u[lo:lo + k] = job['u'][L - 1]
+        inv = inverse.to(device)
+        return dict(u=u[inv], gflat=gflat, start=gs[inv])
 
 
 def start_hvp(h, first, v):

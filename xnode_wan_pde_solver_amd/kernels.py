@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwPathsGradJob, XwPathsHvpJob, XwPathsJetJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
+                   XwPathsGradJob, XwPathsHvpJob, XwPathsJetJob, XwPathsVjpJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -627,6 +627,54 @@ def tiled_paths_jet(jobs, theta, method, H, K, m, work=None):
     else:
         _chk(work, F64, (lib.xw_paths_tiled_jet_work(d, H, K, m) * blocks,), 'work')
     check(lib.xw_paths_tiled_jet(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_jet')
+
+
+def paths_vjp_work(d, H, K, m, tiles, device):
+    """the workspace of one tiled_paths_vjp launch over `tiles` 16-path tiles (xw_paths_tiled_vjp_work doubles per tile: the
+    gradient sweep's vectors and the 16 stage times of the tile's paths)"""
+    per = lib.xw_paths_tiled_vjp_work(d, H, K, m)
+    check(min(per, 0), 'xw_paths_tiled_vjp_work')
+    return torch.empty(per * tiles, dtype=F64, device=device)
+
+
+def tiled_paths_vjp(jobs, theta, method, H, K, m, work=None):
+    """parameter gradients behind tiled_paths_fwd (csrc/xw_tiled_paths_vjp.hip, include/xnwan_vjp.h): job = dict(xT[d,N], start[N],
+    tT[L,N], optional nstep[N] int32, Y[L,H,N] -- as tiled_paths_grad takes them --, a weight per path w[N], the slabs
+    gslab[xw_tiled_ode_bwd_slabs(N), P_u] (P_u = theta's size; zeroed by the launch, every element written) and optional gx[d,N],
+    gs[N]).  With U_p(theta) the DISCRETE final value of path p -- the exact reverse of the steps taken, the grid and the step sizes
+    held fixed, the start value a constant of theta, ReLU gates constants as autograd takes them --: slab_sum(gslab) = sum_p w_p
+    dU_p/dtheta in theta's layout, gx = w_p dU_p/dx_p, gs = w_p dU_p/dstart_p.  A path with w_p = 0 adds exact zeros.  work: the
+    launch's workspace (paths_vjp_work over the jobs' tiles) when the caller brings its own.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    P = theta_size(d, H, K)
+    _chk(theta, F64, (P,), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsVjpJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        if j.get('Y') is None:
+            raise XnwanError('tiled_paths_vjp: Y [L, H, N], the checkpoints of tiled_paths_fwd, is needed (the forward is not recomputed)')
+        _chk(j['Y'], F64, (L, H, N), 'Y')
+        for k in ('w', 'gslab'):
+            if j.get(k) is None:
+                raise XnwanError('tiled_paths_vjp: %s is needed (the weights w [N]; gslab [(N + 15) // 16, P_u], the slabs the '
+                                 'launch writes)' % k)
+        _chk(j['w'], F64, (N,), 'w'); _chk(j['gslab'], F64, (lib.xw_tiled_ode_bwd_slabs(N), P), 'gslab')
+        _chk(j.get('gx'), F64, (d, N), 'gx'); _chk(j.get('gs'), F64, (N,), 'gs')
+        a.xT, a.start, a.tT, a.nstep, a.Y = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep')), _p(j['Y'])
+        a.w, a.gslab, a.gx, a.gs, a.N = _p(j['w']), _p(j['gslab']), _p(j.get('gx')), _p(j.get('gs')), N
+    tiles = sum((a.N + 15) // 16 for a in arr)
+    if work is None:
+        work = paths_vjp_work(d, H, K, m, tiles, theta.device)
+    else:
+        _chk(work, F64, (lib.xw_paths_tiled_vjp_work(d, H, K, m) * tiles,), 'work')
+    check(lib.xw_paths_tiled_vjp(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_vjp')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

@@ -239,6 +239,23 @@ class _DiscFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------------------------------
 # modules
 # ----------------------------------------------------------------------------------------------------------------------
+class _EvalFn(torch.autograd.Function):
+    """XNODE.evaluate_fn: u at scattered points attached to the graph of the module's parameters.  Forward is evaluate(), backward
+    is evaluate_vjp() with the incoming cotangent as the weights -- it runs the checkpointing forward again, chunk by chunk."""
+
+    @staticmethod
+    def forward(ctx, points, net, n_sub, chunk, *params):
+        ctx.net, ctx.n_sub, ctx.chunk = net, n_sub, chunk
+        ctx.save_for_backward(points)
+        return net.evaluate(points, n_sub, chunk=chunk)
+
+    @staticmethod
+    def backward(ctx, gu):
+        points, = ctx.saved_tensors
+        r = ctx.net.evaluate_vjp(points, gu, ctx.n_sub, ctx.chunk)
+        return (None, None, None, None) + tuple(r['params'][n] for n in ctx.net.blob.names)
+
+
 class HiddenField(nn.Module):
     """dh/dt = F([x, t, h]): Linear(H+d+1, K) -> (ReLU -> tied Linear(K, K)) x (layers-1) -> Tanh -> Linear(K, H)."""
 
@@ -407,6 +424,41 @@ class XNODE(nn.Module):
         eigenvectors and eigenvalues of its symmetric part.  Derivatives of the discrete solution, every point's grid held fixed;
         evaluate_hess()'s `lap` without the [M, d, d] output.  Refusals: evaluate_quad()'s, and an `a` of another shape."""
         return self._evaluate_second('evaluate_points_lap', (points, a, n_sub), chunk)
+
+    def evaluate_vjp(self, points, w, n_sub=None, chunk=None):
+        """u_theta at scattered space-time points [M, 1 + d] (time first; host or device) and the weighted sum of its PARAMETER
+        gradients, with a weight per point w [M] -> dict(u [M], params {name: tensor}, start [M]) on the network's device
+        (evalpaths.evaluate_points_vjp): evaluate_grad()'s grids and forward with its checkpoints kept, then a reverse sweep that
+        writes parameter gradients, chunk by chunk.  u: the bits of evaluate().  params: sum_p w_p dU_p/dtheta, one tensor per
+        parameter of this module under its named_parameters() name and in its shape -- U_p the discrete solution at point p, every
+        point's grid and step sizes held fixed, the start value h([T0, x]) a constant of theta, ReLU kinks as autograd takes them:
+        what autograd gives for sum_p w_p u_p through the fixed-grid odeint, every point on a path of its own.  start: w_p
+        dU_p/dstart_p, what reaches the start values (h is not differentiated).
+        Where no point takes a step (every t == T0) the field's (ODE_rhs) entries are tensors of ZEROS, not None.  That differs
+        from forward().backward() on a single time slice, which leaves the field's .grad at None because the reference never puts
+        the field in the graph there and an optimiser must see the same; here there is no reference call to follow -- a cloud
+        mixes points with and without steps, the field is part of the function, and its gradient at such a cloud is zero.
+        Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, points that are not entered
+        at T0, a w of another shape.  chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS, bounded further by the memory of the
+        checkpoints and the slabs, evalpaths.vjp_chunk_paths)."""
+        r = self._evaluate_second('evaluate_points_vjp', (points, w, n_sub), chunk)
+        return dict(u=r['u'], params=dict(zip(self.blob.names, self.blob.split(r['gflat']))), start=r['start'])
+
+    def evaluate_fn(self, points, n_sub=None, chunk=None):
+        """evaluate() attached to the autograd graph of this module's parameters: u [M] on the network's device, so that
+        ((net.evaluate_fn(points) - data) ** 2).mean().backward() and any torch optimiser on the parameters work -- a
+        torch.autograd.Function whose forward is evaluate() and whose backward is evaluate_vjp() with the incoming cotangent as the
+        weights (the gradient of the discrete solution, every point's grid held fixed, the start value a constant of theta).  The
+        backward runs the forward again with its checkpoints kept.  No gradient reaches `points`: points that require grad are
+        refused -- evaluate_grad() gives du/dx.  Refusals otherwise: evaluate_vjp()'s."""
+        if self.blob is None:
+            raise XnwanError('XNODE.bind(device) has not been called')
+        if torch.is_tensor(points) and points.requires_grad:
+            raise XnwanError('evaluate_fn(): points that require grad are not served -- the function is attached to the parameters\' '
+                             'graph only; evaluate_grad() gives du/dx at scattered points')
+        from . import evalpaths
+        evalpaths.vjp_refuse_solver(self.solver)                 # (before the forward runs: evaluate() serves dopri5, the backward would not)
+        return _EvalFn.apply(points, self, n_sub, chunk, *self.blob.params)
 
     def _evaluate_second(self, name, args, chunk, **kw):
         from . import evalpaths

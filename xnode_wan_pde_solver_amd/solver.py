@@ -329,6 +329,15 @@ class NODE_WAN_solver:
         shape.  No collective calls, no random numbers drawn."""
         return self.u_net.module.evaluate_lap(points, a, n_sub, chunk=self.options.eval_chunk_paths)
 
+    def evaluate_vjp(self, points, w, n_sub=None):
+        """the trained solution at scattered space-time points [M, 1 + d] and the weighted sum of its PARAMETER gradients, with a
+        weight per point w [M] -> dict(u [M], params {name: tensor}, start [M]) on the solver's device (XNODE.evaluate_vjp; the
+        fixed-grid solvers: 'dopri5' and 'explicit_adams' are refused).  u: the bits of evaluate(); params: sum_p w_p dU_p/dtheta
+        per parameter of u_net, of the discrete solution with every point's grid held fixed and the start value h a
+        constant of theta -- what a data term sum_p w_p u_p contributes to a loss's gradient; start: w_p dU_p/dstart_p.  Points
+        that are not entered at T0 are refused.  No collective calls (every rank evaluates what it is given), no random numbers drawn."""
+        return self.u_net.module.evaluate_vjp(points, w, n_sub, chunk=self.options.eval_chunk_paths)
+
     def evaluate_residual(self, points, n_sub=None, div_a='autograd'):
         """the strong-form residual of the trained solution at scattered space-time points [M, 1 + d], for the PDE
         du/dt - sum_i d_i (sum_j a_ij d_j u) + b . grad u + c u = f with the solver's own func_a, func_b, func_c, func_f ->
