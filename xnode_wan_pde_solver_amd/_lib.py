@@ -59,6 +59,11 @@ class XwPathsVjpJob(ctypes.Structure):    # include/xnwan_vjp.h: one ragged grou
                 ('gs', c_vp), ('N', c_int)]
 
 
+class XwPathsGvjpJob(ctypes.Structure):   # include/xnwan_grad_vjp.h: one ragged group of xw_paths_tiled_gvjp (XwPathsHvpJob's inputs with Yd read, two weights per path, slabs)
+    _fields_ = [('xT', c_vp), ('start', c_vp), ('tT', c_vp), ('nstep', c_vp), ('Y', c_vp), ('Yd', c_vp), ('vx', c_vp), ('vs', c_vp),
+                ('wu', c_vp), ('wt', c_vp), ('gslab', c_vp), ('N', c_int)]
+
+
 class XwPathsDopriCkptJob(ctypes.Structure):  # include/xnwan_eval_grad.h: XwPathsDopriJob with the checkpoints kept (f.cap slots)
     _fields_ = [('f', XwPathsDopriJob), ('ckpt', c_vp)]
 
@@ -232,6 +237,13 @@ VJP_SIGNATURES = {
 }
 
 
+# the extension header include/xnwan_grad_vjp.h: same conventions
+GVJP_SIGNATURES = {
+    'xw_paths_tiled_gvjp_work': [c_int, c_int, c_int, c_int],
+    'xw_paths_tiled_gvjp': [ctypes.POINTER(XwPathsGvjpJob), c_int, c_f64p, c_int, c_int, c_int, c_int, c_int, c_int, c_f64p, c_vp],
+}
+
+
 class XwSwitches(ctypes.Structure):    # include/xnwan_switches.h: the library's process-wide switches
     _fields_ = [(n, c_int) for n in ('disc_dynamic', 'disc_vin_lds', 'disc_rec_tsum', 'duo_spread', 'reduce_blocks', 'reduce_threads')]
 
@@ -264,7 +276,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(GRAD_SIGNATURES.items())
                            + list(EVAL_GRAD_SIGNATURES.items()) + list(HESS_SIGNATURES.items()) + list(JET_SIGNATURES.items())
-                           + list(VJP_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
+                           + list(VJP_SIGNATURES.items()) + list(GVJP_SIGNATURES.items()) + list(SWITCH_SIGNATURES.items())):
         fn = getattr(lib, name)           # AttributeError here = the .so does not export the declared ABI
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int

@@ -16,7 +16,8 @@
 // path's bits depend neither on its tile neighbours nor on the nstep hint, and a path without a step has hx = hs = 0 exactly.
 // Time is not perturbed.  Lanes past the end of a job walk with the last path and store nothing.  No LDS, no float atomics, no
 // waits between blocks, no read-back: both launches can be captured.
-// The workspace is this source's own (hvp_work): the tiled sweep's (tile_work(1, ...), which the blocks of xw_tiled_blocks.h
+// The workspace is this family's own (hvp_work, xw_tiled_paths_blocks.h, with tfield_tan, tfield_vjp_tan, tile_steps and
+// hvp_prologue: shared with xw_tiled_paths_gvjp.hip): the tiled sweep's (tile_work(1, ...), which the blocks of xw_tiled_blocks.h
 // address) with the tangent vectors behind it.
 #include "xw_common.h"
 #include "xnwan_hess.h"
@@ -24,76 +25,7 @@
 namespace {
 #include "xw_generic_cot.h"   // (not used here: the sweep helpers of xw_tiled_blocks.h name cot_u / cot_job_ok)
 #include "xw_tiled_blocks.h"
-
-// ---- the workspace: the sweep's, then the tangents (offsets in doubles from the tile's base) ----------------------------------------
-struct HvpWork {
-  long vxt, vxp, zd, thd, q, dzd, dzpd, sxd, hvd, vs, total;
-};
-__host__ __device__ inline HvpWork hvp_work(const TileWork& w, int d, int H, int K) {
-  HvpWork x;
-  long p = w.total;
-  x.vxt = p; p += 16L * d;                            // vx of the 16 paths
-  x.vxp = p; p += 16L * K;                            // Win[:, 0..d) vx (no bias): the direction's share of every zd_0
-  x.zd = p; p += 32L * K;                             // tangent pre-activations, gated, two in turn
-  x.thd = p; p += 16L * K;                            // (1 - tz^2) zd_{m-1}: the tangent of tanh(z_{m-1})
-  x.q = p; p += 16L * K;                              // Wo^T a
-  x.dzd = p; p += 16L * K;                            // tangents of the pre-activations' cotangents, ...
-  x.dzpd = p; p += 16L * K;                           //   ... of the layer below
-  x.sxd = p; p += 16L * K;                            // tangent of Sx
-  x.hvd = p; p += 16L * H * 12;                       // the tangents of the sweep's twelve H-vectors
-  x.vs = p; p += 16;                                  // vs of the 16 paths
-  x.total = p;
-  return x;
-}
-
-// fod = dF(t, yin) . (yd, vx) for the tile, behind tfield(.., zs_all = true) at (t, yin), whose z_l and tanh(z_{m-1}) it reads:
-// zd_0 = Win[:, d+1:] yd + vxp, zd_l = Wh gate(zd_{l-1}), thd = (1 - tz^2) zd_{m-1} (with m == 1: of zd_0 itself), fod = Wo thd
-// (fod null: thd only).  Every gate is an epilogue of the product that feeds it.
-__device__ void tfield_tan(const Net& n, const TileWork& w, const HvpWork& x, double* ws, const double* yd, double* fod) {
-  const int K = n.K, H = n.H, ld = n.o.ldin;
-  const double* th = n.th;
-  const double* zs = ws + w.zs;
-  const double* tz = ws + w.th;
-  double* thd = ws + x.thd;
-  const double* in = yd;
-  for (int l = 0; l < n.m; ++l) {
-    const bool top = l == n.m - 1;
-    double* out = top ? thd : ws + x.zd + 16L * K * (l & 1);
-    const int eop = top ? E_TANH_D : E_GATE;
-    const double* aux = top ? tz : zs + 16L * K * l;
-    if (l == 0) tgemm(th + n.o.Win + n.d + 1, ld, 1, K, H, in, A_PLAIN, nullptr, nullptr, 0, 0.0, ws + x.vxp, eop, aux, out);
-    else tgemm(th + n.o.Wh, K, 1, K, K, in, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, eop, aux, out);
-    in = out;
-  }
-  if (fod) tgemm(th + n.o.Wo, K, 1, H, K, thd, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, fod);
-}
-
-// tfield_vjp for (a, ad) at (t, yin) with the tangent yind of yin: gy and Sx as tfield_vjp leaves them, and their tangents
-// gyd (overwritten) and Sxd += dzd_0.  Top: dzd = (Wo^T ad) (1 - tz^2) - 2 (Wo^T a) tz thd; below: the gates alone.
-__device__ void tfield_vjp_tan(const Net& n, const TileWork& w, const HvpWork& x, double* ws, double t, const double* yin,
-                               const double* yind, const double* a, const double* ad, double* gy, double* gyd) {
-  const int K = n.K, H = n.H, ld = n.o.ldin;
-  const double* th = n.th;
-  tfield_vjp(n, w, ws, t, yin, a, gy, nullptr);                      // (leaves every z_l and tz of (t, yin) behind)
-  tfield_tan(n, w, x, ws, yind, nullptr);
-  const double* zs = ws + w.zs;
-  const double* tz = ws + w.th;
-  const double* thd = ws + x.thd;
-  double* q = ws + x.q;
-  double* dzd = ws + x.dzd;
-  double* dzpd = ws + x.dzpd;
-  double* Sxd = ws + x.sxd;
-  tgemm(th + n.o.Wo, 1, K, K, H, a, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, q);
-  tgemm(th + n.o.Wo, 1, K, K, H, ad, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_TANH_D, tz, dzd);
-  for (int e = lane_id(); e < 16 * K; e += 64) dzd[e] -= 2.0 * q[e] * tz[e] * thd[e];
-  sync_tile();
-  for (int l = n.m - 1; l >= 1; --l) {
-    tgemm(th + n.o.Wh, 1, K, K, K, dzd, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, zs + 16L * K * (l - 1), dzpd);
-    double* s_ = dzd; dzd = dzpd; dzpd = s_;
-  }
-  for (int e = lane_id(); e < 16 * K; e += 64) Sxd[e] += dzd[e];
-  tgemm(th + n.o.Win + n.d + 1, 1, ld, H, K, dzd, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gyd);
-}
+#include "xw_tiled_paths_blocks.h"   // HvpWork, tfield_tan, tfield_vjp_tan, tile_steps, hvp_prologue (shared with xw_tiled_paths_gvjp.hip)
 
 // tstep_rk4_bwd with its tangent: v.lam and vd.lam, the cotangent of y_l and its tangent, become those of y_{l-1} (v.Y1, vd.Y1)
 __device__ void tstep_rk4_bwd_tan(const Net& n, const TileWork& w, const HvpWork& x, double* ws, double t0, double dt, const SweepVecs& v,
@@ -135,29 +67,6 @@ __device__ void tstep_rk4_bwd_tan(const Net& n, const TileWork& w, const HvpWork
     vd.lam[e] += vd.g4[e] + vd.g3[e] + vd.g2[e] + vd.gy[e];
   }
   sync_tile();
-}
-
-// the tile's step count (the forward's rule) and, for both kernels, the start values, the direction, x, xproj and vxp
-__device__ __forceinline__ int tile_steps(const int* nstep, int N, int p0, int L) {
-  int ns = L - 1;
-  if (nstep) {
-    int mx = 0;
-    for (int q = 0; q < 16 && p0 + q < N; ++q) mx = nstep[p0 + q] > mx ? nstep[p0 + q] : mx;
-    ns = mx < ns ? mx : ns;
-  }
-  return ns;
-}
-__device__ __forceinline__ void hvp_prologue(const Net& n, const TileWork& w, const HvpWork& x, double* ws, const XwPathsHvpJob& job,
-                                             int p0) {
-  const int N = job.N, l16 = lane_id() & 15;
-  const int pc = p0 + l16 < N ? p0 + l16 : N - 1;
-  if (lane_id() < 16) {
-    ws[w.st + l16] = job.start[pc];
-    ws[x.vs + l16] = job.vs[pc];
-  }
-  tload(n.d, N, p0, job.vx, ws + x.vxt);
-  tile_x(n, w, ws, job.xT, N, p0);                                   // (its sync_tile orders the loads above as well)
-  tgemm(n.th + n.o.Win, n.o.ldin, 1, n.K, n.d, ws + x.vxt, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, ws + x.vxp);
 }
 
 __global__ void __launch_bounds__(64) kt_paths_jvp(XwPathsHvpJob job, const double* __restrict__ theta, int method, int L, int d, int H,

@@ -6,7 +6,8 @@
 // differences: lam = w_p FL_w on row ns, not FL_w; and every VJP, the read-out and the lift's reverse add the tile's parameter
 // gradients to its slab gslab[tile][P_u], kt_ode_bwd's slab format (xw_tiled.hip), so xw_slab_sum and what follows it are unchanged.
 //
-// What the shared blocks cannot serve here, restated below:
+// What the shared blocks cannot serve here, restated in xw_tiled_paths_blocks.h (vfield_vjp, VjpWork: shared with
+// xw_tiled_paths_gvjp.hip) and below (vstep_rk4_bwd):
 //   * tfield_vjp gives the time column of Win one scalar t times the sum of dz over the 16 paths.  Here every path has its own stage
 //     time, so the column needs sum_p t_p dz[r][p]: vfield_vjp keeps the 16 stage times in the workspace (VjpWork.tv) and hands them
 //     to trowsum as its weights.  vstep_rk4_bwd is tstep_rk4_bwd calling it.
@@ -17,55 +18,13 @@
 // Every slab entry is updated by one fixed lane in program order (touter, trowsum): no float atomics, no waits between blocks, no
 // LDS; the same launch twice gives the same bits and the launch can be captured.
 #include "xw_common.h"
+#include "xnwan_hess.h"       // (xw_tiled_paths_blocks.h names XwPathsHvpJob)
 #include "xnwan_vjp.h"
 
 namespace {
 #include "xw_generic_cot.h"   // (not used by this sweep: the sweep helpers of xw_tiled_blocks.h name cot_u / cot_job_ok)
 #include "xw_tiled_blocks.h"
-
-// behind the tile's TileWork: the stage times of the 16 paths (the weights w_p live in TileWork.ub, the cotangent on u)
-struct VjpWork {
-  long tv, total;
-};
-__host__ __device__ inline VjpWork vjp_work(const TileWork& w) {
-  VjpWork x;
-  x.tv = w.total;
-  x.total = w.total + 16;
-  return x;
-}
-
-// tfield_vjp with a stage time PER PATH (t: the lane's own path's, column lane & 15) and a slab: a^T dF/d(y, theta) at (t, yin) --
-// gy (overwritten), Sx += cotangent of z_0, parameter gradients into slab.  tfield_vjp's operations in tfield_vjp's order; the time
-// column of Win takes sum_p tv[p] dz[r][p]
-__device__ void vfield_vjp(const Net& n, const TileWork& w, const VjpWork& x, double* ws, double t, const double* yin, const double* a,
-                           double* gy, double* slab) {
-  const int K = n.K, H = n.H, ld = n.o.ldin;
-  const double* th = n.th;
-  double* tv = ws + x.tv;
-  if (lane_id() < 16) tv[lane_id()] = t;                         // (ordered before its reader by tfield's sync_tile)
-  tfield(n, w, ws, t, yin, nullptr, true);
-  const double* zs = ws + w.zs;
-  const double* tz = ws + w.th;
-  double* dz = ws + w.dz;
-  double* dzp = ws + w.dzp;
-  double* Sx = ws + w.total - 16L * K;
-  // dz = (Wo^T a) (1 - tanh^2)
-  tgemm(th + n.o.Wo, 1, K, K, H, a, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_TANH_D, tz, dz);
-  touter(slab, n.o.Wo, K, H, K, a, tz, A_PLAIN);
-  trowsum(slab, n.o.Wob, 1, H, a, nullptr, 1.0);
-  for (int l = n.m - 1; l >= 1; --l) {
-    const double* zp = zs + 16L * K * (l - 1);
-    touter(slab, n.o.Wh, K, K, K, dz, zp, A_RELU);
-    trowsum(slab, n.o.Whb, 1, K, dz, nullptr, 1.0);
-    tgemm(th + n.o.Wh, 1, K, K, K, dz, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_GATE, zp, dzp);
-    double* s_ = dz; dz = dzp; dzp = s_;
-  }
-  touter(slab, (long)n.o.Win + n.d + 1, ld, K, H, dz, yin, A_PLAIN);
-  trowsum(slab, (long)n.o.Win + n.d, ld, K, dz, tv, 1.0);
-  for (int e = lane_id(); e < 16 * K; e += 64) Sx[e] += dz[e];
-  // gy = Win[:, d+1:]^T dz
-  tgemm(th + n.o.Win + n.d + 1, 1, ld, H, K, dz, A_PLAIN, nullptr, nullptr, 0, 0.0, nullptr, E_NONE, nullptr, gy);
-}
+#include "xw_tiled_paths_blocks.h"   // VjpWork, vfield_vjp (shared with xw_tiled_paths_gvjp.hip)
 
 // tstep_rk4_bwd on vfield_vjp (no further cotangent on k1): v.lam, the cotangent of y_l, becomes that of y_{l-1} (in v.Y1)
 __device__ __forceinline__ void vstep_rk4_bwd(const Net& n, const TileWork& w, const VjpWork& x, double* ws, double t0, double dt,

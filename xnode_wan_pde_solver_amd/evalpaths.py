@@ -32,7 +32,12 @@ point's own grid, R directions per point in one launch per chunk -- no reverse s
 
 Parameter gradients come from evaluate_points_vjp (behind XNODE.evaluate_vjp / evaluate_fn and NODE_WAN_solver.evaluate_vjp), for
 the fixed-grid schemes: the forward with its checkpoints kept, then kernels.tiled_paths_vjp (csrc/xw_tiled_paths_vjp.hip), the
-gradient sweep with a weight per point that writes a slab per tile, and kernels.slab_sum into one flat gradient, chunk by chunk."""
+gradient sweep with a weight per point that writes a slab per tile, and kernels.slab_sum into one flat gradient, chunk by chunk.
+
+Parameter gradients of du/dx and ut as well come from evaluate_points_grad_vjp (behind XNODE.evaluate_grad_vjp / evaluate_grad_fn
+and NODE_WAN_solver.evaluate_grad_vjp): the forward, the gradient sweep and the tangent forward of kernels.tiled_paths_hvp, then
+kernels.tiled_paths_gvjp (csrc/xw_tiled_paths_gvjp.hip), the tangent of the slab-writing sweep along (wg, dh/dx . wg) with the
+weights on u and ut folded into its start."""
 import types
 
 import torch
@@ -547,6 +552,93 @@ def evaluate_points_hvp(points, v, n_sub, setup, domain, solver, h, theta, metho
         grad = gx.t()[inv] + gs[inv].view(-1, 1) * dh
         hvp = hx[0].t()[inv] + hs[0][inv].view(-1, 1) * dh + gs[inv].view(-1, 1) * d2
         return dict(u=u[inv], grad=grad.contiguous(), dv=ju[0][inv], hvp=hvp.contiguous())
+
+
+# ---- parameter gradients of u, du/dx and ut: a weighted sum over the cloud ----------------------------------------------------------
+def gvjp_chunk_paths(chunk, L, H, P):
+    """paths per launch of evaluate_points_grad_vjp: a chunk's checkpoints Y and tangent checkpoints Yd, [L, H, n] each, and its
+    slabs [tiles, P] (P = theta's size) stay below EVAL_GRAD_CKPT_BYTES together, 8 (2 L H n + P tiles) with n = 16 tiles (whole
+    16-path tiles, at least one) -- a memory bound, not a tuned number"""
+    return min(chunk, 16 * max(1, EVAL_GRAD_CKPT_BYTES // (8 * (2 * 16 * L * H + P))))
+
+
+def grad_vjp_refuse_solver(solver):
+    """XnwanError for the solvers evaluate_points_grad_vjp does not serve (XNODE.evaluate_grad_fn asks before its forward runs)"""
+    if solver in REFUSED_SOLVERS:
+        raise XnwanError("evaluate_grad_vjp(): solver %r is not served -- parameter gradients of du/dx and ut at scattered points run "
+                         "the fixed-grid schemes %s only (the tangent of the reverse of the steps taken, with slabs; no per-path "
+                         "record sweep or multistep history is differentiated twice)" % (solver, sorted(KN.METHODS)))
+
+
+def evaluate_points_grad_vjp(points, wu, wg, wt, n_sub, setup, domain, solver, h, theta, method, H, K, m, device,
+                             chunk=EVAL_CHUNK_PATHS):
+    """u_theta, its gradient in x and its time derivative at points [M, 1 + d] (time first; host or device, float32 or float64) and
+    the PARAMETER gradient of their weighted sum, with weights wu [M], wg [M, d], wt [M] (each may be None: zeros; not all three)
+    -> dict(u [M], grad [M, d], ut [M], gflat [P_u]), float64 on `device`.  Entry rule, refusals, step counts, packing and sort are
+    second_order_entry's; per chunk (gvjp_chunk_paths) kernels.tiled_paths_fwd keeps the checkpoints, kernels.tiled_paths_grad gives
+    grad and ut, kernels.tiled_paths_hvp with ju alone runs the tangent forward along (wg, dh/dx . wg), kernels.tiled_paths_gvjp
+    walks both sets of checkpoints back and kernels.slab_sum adds the chunk's slabs to gflat:
+      u, grad, ut  the bits of evaluate_points_grad
+      gflat        d/dtheta sum_p [wu_p U_p + wg_p . dU_p/dx + wt_p ut_p] in theta's layout (P_u = theta's size).  U_p is the DISCRETE
+                   solution at point p as evaluate_points_vjp differentiates it: every point's grid and step sizes held fixed, the
+                   start value h([T0, x]) AND its gradient dh/dx constants of theta, ReLU kinks as autograd takes them; dU_p/dx is
+                   evaluate_points_grad's grad, gx + gs dh/dx, so wg_p . dU_p/dx is the derivative of (x, s) -> U_p along
+                   (wg_p, dh/dx . wg_p).  ut_p = FL_w . F(t_p, x_p, y(t_p)) belongs to the CONTINUOUS model; theta enters it through
+                   the read-out, the field and y(t_p), the last by the same discrete reverse.  The chunks go in sorted order, so the
+                   bits are a function of the inputs and `chunk`.  Exact zeros for an empty cloud.
+    Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, every point that is not entered
+    at T0, wu, wg and wt all None, and a weight of another shape.  No collective calls, no random numbers."""
+    who = 'evaluate_grad_vjp()'
+    grad_vjp_refuse_solver(solver)
+    with torch.no_grad():
+        e = second_order_entry(who, points, n_sub, setup, domain, solver, h, device, chunk)
+        M, d = points.shape[0], setup['dim']
+        if wu is None and wg is None and wt is None:
+            raise XnwanError('%s: nothing to differentiate: at least one of wu [M], wg [M, d], wt [M] must be given' % who)
+        for name, a, shape in (('wu', wu, (M,)), ('wg', wg, (M, d)), ('wt', wt, (M,))):
+            if a is not None and not (torch.is_tensor(a) and tuple(a.shape) == shape):
+                raise XnwanError('%s: %s must be None or a tensor %s, a weight per point (got %s)'
+                                 % (who, name, list(shape), tuple(a.shape) if torch.is_tensor(a) else type(a).__name__))
+        P = KN.theta_size(d, H, K)
+        new = lambda *shape: torch.empty(*shape, dtype=F64, device=device)   # noqa: E731
+        gflat = torch.zeros(P, dtype=F64, device=device)
+        if e is None:
+            return dict(u=new(0), grad=new(0, d), ut=new(0), gflat=gflat)
+        od, dh = e.order.to(device), e.dh.to(device)
+        sort = lambda a: None if a is None else a.detach().to(F64).to(device)[od].contiguous()   # noqa: E731
+        wus, wts = sort(wu), sort(wt)
+        vxT = vs = None
+        if wg is not None:
+            vd = wg.detach().to(F64).to(device)
+            vxT, vs = vd[od].t().contiguous(), (dh * vd).sum(1)[od].contiguous()
+        L = e.tT.shape[0]
+        per = gvjp_chunk_paths(chunk, L, H, P)
+        u, gx, gs, ut = new(M), new(d, M), new(M), new(M)
+        for lo in range(0, M, per):
+            k = min(lo + per, M) - lo
+            whole = k == M
+            cut = (lambda a: a) if whole else (lambda a: a[:, lo:lo + k].contiguous())
+            job = dict(xT=cut(e.xT), start=e.start[lo:lo + k], tT=cut(e.tT), nstep=e.nstep[lo:lo + k], u=new(L, k), Y=new(L, H, k))
+            KN.tiled_paths_fwd([job], theta, method, H, K, m)
+            g = dict(gx=gx if whole else new(d, k), gs=gs[lo:lo + k], ut=ut[lo:lo + k])
+            KN.tiled_paths_grad([dict(job, **g)], theta, method, H, K, m)
+            u[lo:lo + k] = job['u'][L - 1]
+            if not whole:
+                gx[:, lo:lo + k] = g['gx']
+            tiles = (k + 15) // 16
+            o = dict(gslab=new(tiles, P))
+            if wus is not None:
+                o['wu'] = wus[lo:lo + k]
+            if wts is not None:
+                o['wt'] = wts[lo:lo + k]
+            if vxT is not None:
+                o.update(vx=cut(vxT), vs=vs[lo:lo + k], Yd=new(L, H, k))
+                KN.tiled_paths_hvp([dict(job, ju=new(k), **{n: o[n] for n in ('vx', 'vs', 'Yd')})], theta, method, H, K, m)
+            KN.tiled_paths_gvjp([dict(job, **o)], theta, method, H, K, m)
+            KN.slab_sum(o['gslab'], out=gflat, accumulate=True)
+        inv = e.inv
+        grad = gx.t()[inv] + gs[inv].view(-1, 1) * dh
+        return dict(u=u[inv], grad=grad.contiguous(), ut=ut[inv], gflat=gflat)
 
 
 def evaluate_points_hess(points, n_sub, setup, domain, solver, h, theta, method, H, K, m, device, chunk=EVAL_CHUNK_PATHS):

@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._lib import (lib, check, XnwanError, XwOdeFwdJob, XwOdeBwdJob, XwDopriJob, XwDopriSweepJob, XwPathsJob, XwPathsDopriJob,
-                   XwPathsGradJob, XwPathsHvpJob, XwPathsJetJob, XwPathsVjpJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
+                   XwPathsGradJob, XwPathsHvpJob, XwPathsJetJob, XwPathsVjpJob, XwPathsGvjpJob, XwPathsDopriCkptJob, XwPathsDopriGradJob, XwSwitches)
 from .options import EngineOptions
 
 METHODS = {'euler': 0, 'midpoint': 1, 'rk4': 2}
@@ -675,6 +675,66 @@ def tiled_paths_vjp(jobs, theta, method, H, K, m, work=None):
     else:
         _chk(work, F64, (lib.xw_paths_tiled_vjp_work(d, H, K, m) * tiles,), 'work')
     check(lib.xw_paths_tiled_vjp(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_vjp')
+
+
+def paths_gvjp_work(d, H, K, m, tiles, device):
+    """the workspace of one tiled_paths_gvjp launch over `tiles` 16-path tiles (xw_paths_tiled_gvjp_work doubles per tile: the
+    Hessian-vector sweep's vectors, the stage times and weights of the tile's paths and a tangent per layer of the field)"""
+    per = lib.xw_paths_tiled_gvjp_work(d, H, K, m)
+    check(min(per, 0), 'xw_paths_tiled_gvjp_work')
+    return torch.empty(per * tiles, dtype=F64, device=device)
+
+
+def tiled_paths_gvjp(jobs, theta, method, H, K, m, work=None):
+    """parameter gradients of u, of its derivative along a direction and of ut behind tiled_paths_fwd (csrc/xw_tiled_paths_gvjp.hip,
+    include/xnwan_grad_vjp.h): job = dict(xT[d,N], start[N], tT[L,N], optional nstep[N] int32, Y[L,H,N] -- as tiled_paths_grad takes
+    them --, the slabs gslab[xw_tiled_ode_bwd_slabs(N), P_u] (P_u = theta's size; zeroed by the launch, every element written) and at
+    least one of: wu[N], a weight on u; wt[N], a weight on ut; the direction vx[d,N] with vs[N] and Yd[L,H,N], the tangent
+    checkpoints that tiled_paths_hvp wrote for this direction (run it with ju alone first: Yd is READ here)).  With U_p(theta; x, s)
+    the DISCRETE final value of path p -- the exact reverse of the steps taken, the grid and the step sizes held fixed, the start
+    value and the direction constants of theta, ReLU gates constants as autograd takes them -- and ut_p = FL_w . F(t_p, x_p, y(t_p)):
+    slab_sum(gslab) = d/dtheta sum_p [wu_p U_p + (dU_p/dx . vx_p + dU_p/ds vs_p) + wt_p ut_p] in theta's layout.  A path whose
+    weights and direction are zero adds exact zeros.  work: the launch's workspace (paths_gvjp_work over the jobs' tiles) when the
+    caller brings its own.  One L for all jobs of a launch."""
+    _need_gpu()
+    d = jobs[0]['xT'].shape[0]
+    L = jobs[0]['tT'].shape[0]
+    P = theta_size(d, H, K)
+    _chk(theta, F64, (P,), 'theta')
+    if method not in METHODS.values():
+        raise XnwanError('per-path time grids run the fixed-grid methods %s only (no per-path step controller or history is built)'
+                         % sorted(METHODS))
+    arr = (XwPathsGvjpJob * len(jobs))()
+    for a, j in zip(arr, jobs):
+        N = j['xT'].shape[1]
+        _chk(j['xT'], F64, (d, N), 'xT'); _chk(j['start'], F64, (N,), 'start'); _chk(j['tT'], F64, (L, N), 'tT')
+        _chk(j.get('nstep'), torch.int32, (N,), 'nstep')
+        if j.get('Y') is None:
+            raise XnwanError('tiled_paths_gvjp: Y [L, H, N], the checkpoints of tiled_paths_fwd, is needed (the forward is not recomputed)')
+        _chk(j['Y'], F64, (L, H, N), 'Y')
+        if j.get('gslab') is None:
+            raise XnwanError('tiled_paths_gvjp: gslab [(N + 15) // 16, P_u], the slabs the launch writes, is needed')
+        _chk(j['gslab'], F64, (lib.xw_tiled_ode_bwd_slabs(N), P), 'gslab')
+        direction = j.get('vx') is not None
+        if direction != (j.get('vs') is not None):
+            raise XnwanError('tiled_paths_gvjp: vx [d, N] and vs [N] are one direction: both or neither')
+        if direction and j.get('Yd') is None:
+            raise XnwanError('tiled_paths_gvjp: Yd [L, H, N], the tangent checkpoints tiled_paths_hvp wrote for (vx, vs), is needed '
+                             'with a direction (the tangent forward is not recomputed)')
+        if not direction and j.get('wu') is None and j.get('wt') is None:
+            raise XnwanError('tiled_paths_gvjp: nothing to differentiate (at least one of wu, wt, vx with vs)')
+        _chk(j.get('vx'), F64, (d, N), 'vx'); _chk(j.get('vs'), F64, (N,), 'vs')
+        _chk(j.get('Yd') if direction else None, F64, (L, H, N), 'Yd')
+        _chk(j.get('wu'), F64, (N,), 'wu'); _chk(j.get('wt'), F64, (N,), 'wt')
+        a.xT, a.start, a.tT, a.nstep, a.Y = _p(j['xT']), _p(j['start']), _p(j['tT']), _p(j.get('nstep')), _p(j['Y'])
+        a.Yd, a.vx, a.vs = _p(j.get('Yd') if direction else None), _p(j.get('vx')), _p(j.get('vs'))
+        a.wu, a.wt, a.gslab, a.N = _p(j.get('wu')), _p(j.get('wt')), _p(j['gslab']), N
+    tiles = sum((a.N + 15) // 16 for a in arr)
+    if work is None:
+        work = paths_gvjp_work(d, H, K, m, tiles, theta.device)
+    else:
+        _chk(work, F64, (lib.xw_paths_tiled_gvjp_work(d, H, K, m) * tiles,), 'work')
+    check(lib.xw_paths_tiled_gvjp(arr, len(jobs), _p(theta), method, L, d, H, K, m, _p(work), _stream()), 'xw_paths_tiled_gvjp')
 
 
 def tiled_ode_bwd(xT, t, start, theta, Y, ubar, method, H, K, m, want_x=True, want_params=False):

@@ -256,6 +256,29 @@ class _EvalFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(r['params'][n] for n in ctx.net.blob.names)
 
 
+class _EvalGradFn(torch.autograd.Function):
+    """XNODE.evaluate_grad_fn: u, du/dx and ut at scattered points attached to the graph of the module's parameters.  Forward is
+    evaluate_grad(), backward is evaluate_grad_vjp() with the incoming cotangents as the weights -- it runs the checkpointing
+    forward again, chunk by chunk.  A cotangent that is missing or all zero becomes None (its term is not swept)."""
+
+    @staticmethod
+    def forward(ctx, points, net, n_sub, chunk, *params):
+        ctx.net, ctx.n_sub, ctx.chunk = net, n_sub, chunk
+        ctx.save_for_backward(points)
+        ctx.set_materialize_grads(False)
+        r = net.evaluate_grad(points, n_sub, chunk)
+        return r['u'], r['grad'], r['ut']
+
+    @staticmethod
+    def backward(ctx, gu, gg, gt):
+        points, = ctx.saved_tensors
+        gu, gg, gt = (None if g is None or not bool((g != 0).any()) else g for g in (gu, gg, gt))
+        if gu is None and gg is None and gt is None:
+            return (None, None, None, None) + tuple(torch.zeros_like(p) for p in ctx.net.blob.params)
+        r = ctx.net.evaluate_grad_vjp(points, gu, gg, gt, ctx.n_sub, ctx.chunk)
+        return (None, None, None, None) + tuple(r['params'][n] for n in ctx.net.blob.names)
+
+
 class HiddenField(nn.Module):
     """dh/dt = F([x, t, h]): Linear(H+d+1, K) -> (ReLU -> tied Linear(K, K)) x (layers-1) -> Tanh -> Linear(K, H)."""
 
@@ -459,6 +482,44 @@ class XNODE(nn.Module):
         from . import evalpaths
         evalpaths.vjp_refuse_solver(self.solver)                 # (before the forward runs: evaluate() serves dopri5, the backward would not)
         return _EvalFn.apply(points, self, n_sub, chunk, *self.blob.params)
+
+    def evaluate_grad_vjp(self, points, wu=None, wg=None, wt=None, n_sub=None, chunk=None):
+        """u_theta, its gradient in x and its time derivative at scattered space-time points [M, 1 + d] (time first; host or
+        device) and the PARAMETER gradient of their weighted sum, with weights wu [M], wg [M, d], wt [M] (each may be None: zeros;
+        not all three) -> dict(u [M], grad [M, d], ut [M], params {name: tensor}) on the network's device
+        (evalpaths.evaluate_points_grad_vjp): evaluate_grad()'s launches, then the tangent of evaluate_vjp()'s sweep along
+        (wg, dh/dx . wg), chunk by chunk.  u, grad, ut: the bits of evaluate_grad().  params: d/dtheta sum_p [wu_p u_p + wg_p .
+        grad_p + wt_p ut_p] in evaluate_vjp()'s layout and names -- of the discrete solution, every point's grid and step sizes held
+        fixed, the start value h([T0, x]) and its gradient dh/dx constants of theta, ReLU kinks as autograd takes them: what
+        autograd gives for that sum with create_graph on the x-gradient, every point on a path of its own.  ut is the CONTINUOUS
+        model's time derivative FL_w . F(t, x, y(t)); theta enters it through the read-out, the field and y(t).  The field's
+        entries are tensors of zeros, not None, where nothing reaches them (evaluate_vjp() says why).
+        Refused: the solvers 'dopri5' and 'explicit_adams', a domain class without `entry`, t < t_in, points that are not entered
+        at T0, all three weights None, a weight of another shape.  chunk: paths per launch (evalpaths.EVAL_CHUNK_PATHS, bounded
+        further by the memory of both sets of checkpoints and the slabs, evalpaths.gvjp_chunk_paths)."""
+        r = self._evaluate_second('evaluate_points_grad_vjp', (points, wu, wg, wt, n_sub), chunk)
+        return dict(u=r['u'], grad=r['grad'], ut=r['ut'], params=dict(zip(self.blob.names, self.blob.split(r['gflat']))))
+
+    def evaluate_grad_fn(self, points, n_sub=None, chunk=None):
+        """evaluate_grad() attached to the autograd graph of this module's parameters: dict(u [M], grad [M, d], ut [M]) on the
+        network's device, so that a first-order strong-form residual or a flux fit trains --
+            r = net.evaluate_grad_fn(pts)
+            loss = ((r['ut'] + (B * r['grad']).sum(1) + c * r['u'] - f) ** 2).mean() + ((r['grad'] - flux) ** 2).mean()
+            loss.backward(); opt.step()
+        -- ONE torch.autograd.Function with three outputs whose forward is evaluate_grad() and whose backward is
+        evaluate_grad_vjp() with the incoming cotangents as the weights (a missing or all-zero cotangent: None).  The backward
+        runs the forward again with its checkpoints kept.  What is held fixed is evaluate_grad_vjp()'s: grids, step sizes, h and
+        dh/dx.  No gradient reaches `points`, and no second derivative in theta is built (the outputs' graph ends at this
+        Function): points that require grad are refused.  Refusals otherwise: evaluate_grad_vjp()'s."""
+        if self.blob is None:
+            raise XnwanError('XNODE.bind(device) has not been called')
+        if torch.is_tensor(points) and points.requires_grad:
+            raise XnwanError('evaluate_grad_fn(): points that require grad are not served -- the function is attached to the '
+                             'parameters\' graph only; evaluate_hvp() gives the derivative of du/dx in x')
+        from . import evalpaths
+        evalpaths.grad_vjp_refuse_solver(self.solver)            # (before the forward runs: evaluate_grad() serves dopri5, the backward would not)
+        u, grad, ut = _EvalGradFn.apply(points, self, n_sub, chunk, *self.blob.params)
+        return dict(u=u, grad=grad, ut=ut)
 
     def _evaluate_second(self, name, args, chunk, **kw):
         from . import evalpaths

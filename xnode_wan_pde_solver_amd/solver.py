@@ -338,6 +338,17 @@ class NODE_WAN_solver:
         that are not entered at T0 are refused.  No collective calls (every rank evaluates what it is given), no random numbers drawn."""
         return self.u_net.module.evaluate_vjp(points, w, n_sub, chunk=self.options.eval_chunk_paths)
 
+    def evaluate_grad_vjp(self, points, wu=None, wg=None, wt=None, n_sub=None):
+        """the trained solution, its gradient in x and its time derivative at scattered space-time points [M, 1 + d] and the
+        PARAMETER gradient of their weighted sum, with weights wu [M], wg [M, d], wt [M] (each may be None, not all three) ->
+        dict(u [M], grad [M, d], ut [M], params {name: tensor}) on the solver's device (XNODE.evaluate_grad_vjp; the fixed-grid
+        solvers: 'dopri5' and 'explicit_adams' are refused).  u, grad, ut: the bits of evaluate_grad(); params: d/dtheta sum_p
+        [wu_p u_p + wg_p . grad_p + wt_p ut_p] per parameter of u_net, of the discrete solution with every point's grid held
+        fixed and the start value h and its gradient constants of theta -- what a flux, Sobolev or first-order residual term
+        contributes to a loss's gradient.  Points that are not entered at T0 are refused.  No collective calls (every rank
+        evaluates what it is given), no random numbers drawn."""
+        return self.u_net.module.evaluate_grad_vjp(points, wu, wg, wt, n_sub, chunk=self.options.eval_chunk_paths)
+
     def evaluate_residual(self, points, n_sub=None, div_a='autograd'):
         """the strong-form residual of the trained solution at scattered space-time points [M, 1 + d], for the PDE
         du/dt - sum_i d_i (sum_j a_ij d_j u) + b . grad u + c u = f with the solver's own func_a, func_b, func_c, func_f ->
